@@ -16,7 +16,20 @@ exchange one (2H+2)-double softmax record per step with one RCCL all-gather.
 same config on its own GPU alone (`speedup_vs_1`), and the `c4` leg (K=1,048,576,
 the north-star scaling config) is run beside the headline at every N.
 
-Launch: python bench.py [--config c3|c4|c5] [--steps K --warmup W]  (N=1);
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does what the headline figure needs and
+nothing else: set-up, the pre-warm and W warm-up steps, the K timed steps, the output dump if
+`--dump-outputs DIR` is given, and the result line.  `--full` adds every other measurement: the CPU
+baseline, the synchronous-mode pass, the kernel-timing passes behind `roofline`, `speedup_vs_1` and the
+group parity check for N>1, and the C4, C4-shard, cadence, bilinear, C2, C5 and costmap-builder legs
+(each of which `--no-...` can still drop).
+
+`--dump-outputs DIR` writes what the last timed step of the headline pass returned to its caller
+(the eight arrays of `outputs()`: controls, velocities and the optimal rollout) and that step's
+per-trajectory costs as float32 `DIR/<name>.npy`.  The headline pass starts from the zero nominal
+controls and fixed step counters, so the same arguments give the same inputs in every run and two
+builds can be compared array for array.
+
+Launch: python bench.py [--config c3|c4|c5] [--steps K --warmup W] [--full] [--dump-outputs DIR]  (N=1);
         python bench.py --gpus N: one process drives GPUs 0..N-1 through the C-ABI group
         (mppi_group_create: one context per GPU, ncclCommInitAll, one ncclAllGather per member
         per step, each member's launches enqueued by its own thread; SURVEY.md §8(e));
@@ -93,7 +106,19 @@ def parse():
     ap.add_argument("--group-devices", default=None,
                     help="comma-separated device of each group member (default with --gpus N>1 and no "
                          "torch.distributed launcher: 0,1,...,N-1)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CPU baseline, synchronous-mode pass, "
+                         "kernel-timing passes (roofline), N=1 reference and parity for N>1, and the C4, "
+                         "shard, cadence, bilinear, C2, C5 and costmap legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs and costs of the headline pass's last timed step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline pass only
+        args.cpu_baseline_seconds = 0.0
+        args.no_sync_pass = args.no_c4 = args.no_c5 = args.no_shard = True
+        args.no_cadence = args.no_bilinear = args.no_costmap = True
+    return args
 
 
 def source_hash():
@@ -374,6 +399,16 @@ class Runner:
     def outputs(self):
         return self.group.outputs() if self.group is not None else self.eng.outputs()
 
+    def reset_nominal(self):
+        zero = np.zeros(self.H, np.float32)
+        for e in self.engines:
+            e.set_nominal(zero, zero)
+
+    def costs(self):
+        """The last step's cost of every trajectory this process holds (a rank's shard under torch.distributed)."""
+        c = self.group.costs() if self.group is not None else self.eng.costs()
+        return c[:self.k_local] if self.group is None else c
+
     def step(self, proj, i):
         if self.group is not None:
             self.group.step(proj, i, copy=False)
@@ -411,11 +446,15 @@ def group_parity(cfg, devices, proj, steps=3):
     return bool(same)
 
 
-def timed_run(torch, dist, run, proj, warmup, steps, step0, async_tail, kernel_timing=False):
+def timed_run(torch, dist, run, proj, warmup, steps, step0, async_tail, kernel_timing=False, reset=False):
     """`warmup` untimed + `steps` timed MPPI steps, barrier + synchronize on both sides; returns
     the max-over-ranks wall time of the timed steps.  Kernel timing (if any) on the first
-    member's / rank's engine."""
+    member's / rank's engine.  `reset`: start from the zero nominal controls, so that the steps'
+    inputs do not depend on what ran on the engines before.  The last timed step's outputs, as its
+    caller receives them, are kept in `run.last`."""
     eng = run.eng
+    if reset:
+        run.reset_nominal()
     run.set_async_tail(async_tail)
     eng.set_timing(False)
     for i in range(warmup):
@@ -435,7 +474,7 @@ def timed_run(torch, dist, run, proj, warmup, steps, step0, async_tail, kernel_t
     t0 = time.perf_counter()
     for i in range(steps):
         run.step(proj, step0 + warmup + i)
-    run.outputs()          # the last step's deferred optimal rollout is in host memory too
+    run.last = run.outputs()   # the last step's deferred optimal rollout is in host memory too
     barrier()
     el = time.perf_counter() - t0
     if dist is not None and run.world > 1:
@@ -599,6 +638,13 @@ def cadence_bench(torch, device, proj, frames=40):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 .npy per array."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def chain_static(path=os.path.join(ROOT, "profiles", "isa", "chain_count.json")):
     """The chain step's static instruction count (profiles/isa/chain_count.py) if it was taken
     from the current kernel sources, else None."""
@@ -688,18 +734,20 @@ def main():
     nt = max(args.steps // 4, 10)
     srv0 = run.eng.server_time()
     el = timed_run(torch, dist, run, args.proj, args.warmup, args.steps, s0, not args.sync,
-                   kernel_timing=2 if args.timed_events else 0)
+                   kernel_timing=2 if args.timed_events else 0, reset=True)
+    dump = dict(run.last, costs=run.costs()) if args.dump_outputs and rank == 0 else None
     head_info = run.eng.launch_info()   # the schedule the timed steps ran on
     srv1 = run.eng.server_time()
     n_srv = srv1[2] - srv0[2]   # the server's own clock over that pass (its warm-up steps included)
     srv_roll_us = (srv1[0] - srv0[0]) / n_srv if n_srv > 0 else None
     srv_step_us = (srv1[1] - srv0[1]) / n_srv if n_srv > 0 else None
-    if not args.timed_events:
+    if args.full and not args.timed_events:
         timed_run(torch, dist, run, args.proj, args.warmup, nt, 2 * s0, not args.sync, kernel_timing=2)
     roll_ms, _, n_roll = run.eng.timing()
     # the finish and the tail in a pass of their own (mode 1 waits for the stream and for each tail
     # on the host, which moves the tail onto the next rollout)
-    timed_run(torch, dist, run, args.proj, args.warmup, nt, 3 * s0, not args.sync, kernel_timing=1)
+    if args.full:
+        timed_run(torch, dist, run, args.proj, args.warmup, nt, 3 * s0, not args.sync, kernel_timing=1)
     _, fin_ms, n_fin = run.eng.timing()
     tail_ms, n_tail = run.eng.tail_timing()
     info = run.eng.launch_info()
@@ -707,6 +755,8 @@ def main():
     record_bytes = run.eng.record_len() * 8
     k_local = run.k_local
     run.close()
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump)
 
     def solo_rate(cfg, steps):
         """rank 0 / member 0 alone, the whole config on its GPU (the N=1 reference of this job)."""
@@ -716,14 +766,16 @@ def main():
         return steps / t
 
     speedup = None
-    if world > 1:
+    if not args.full:
+        pass   # the N=1 reference and the parity check are runs of their own
+    elif world > 1:
         dist.barrier()
         if rank == 0:
             speedup = (args.steps / el) / solo_rate(args.config, args.steps)
         dist.barrier()
     elif members > 1:
         speedup = (args.steps / el) / solo_rate(args.config, args.steps)
-    parity = group_parity(args.config, devices, args.proj) if devices is not None and members > 1 else None
+    parity = group_parity(args.config, devices, args.proj) if args.full and devices is not None and members > 1 else None
 
     c4 = None
     if not args.no_c4 and args.config != "c4":
@@ -766,7 +818,7 @@ def main():
         steps_per_s = args.steps / el
         k_avg_ms = roll_ms / max(n_roll, 1)
         alg_bytes = BYTES_PER_ROLLOUT_STEP * k_local * H
-        achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9
+        achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9 if n_roll else None
         # the rollout kernel the plan chose: role split (1024-thread workgroups) or pair (512); the
         # headline steps run its body inside the resident step server, the kernel time comes from
         # the separate-launch timing pass (the same rollout body, HIP events around each launch)
@@ -812,7 +864,7 @@ def main():
                 "server_step_us": round(srv_step_us, 2) if srv_step_us else None,
                 "server_clock_steps": n_srv,
                 "server_clock": "s_memrealtime on the server: command seen -> last rollout ticket / -> completion word, averaged",
-                "finish_kernel_avg_ms": round(fin_ms / max(n_fin, 1), 5),
+                "finish_kernel_avg_ms": round(fin_ms / n_fin, 5) if n_fin else None,
                 "chain": {"instructions_per_step": chain_static(),
                           "cycles_per_step": round(clock["cycles_per_step"], 1),
                           "shader_clock_mhz": round(clock["shader_mhz"], 1),
@@ -827,7 +879,9 @@ def main():
                 "tail_kernel_avg_ms": round(tail_ms / n_tail, 5) if n_tail else None,
                 "src_sha256": source_hash(),
             },
-            "roofline": {
+        }
+        if n_roll:   # the rollout kernel was timed (--full's pass of its own, or --timed-events)
+            rec["roofline"] = {
                 "bound": "hbm",
                 "achieved": round(achieved, 2),
                 "peak": HBM_PEAK_GBS,
@@ -840,8 +894,7 @@ def main():
                 "kernel_timing": "HIP events around each launch of a separate-launch pass (mppi_set_timing(2)): "
                                  "the launch waits for the side streams' work, so no noise or tail kernel runs beside it",
                 "algorithmic_bytes_per_launch": alg_bytes,
-            },
-        }
+            }
         if c4 is not None:
             rec["c4"] = c4
         # (the shard leg before the bilinear one: after the C4 and bilinear legs the plain K = 131 072

@@ -30,7 +30,7 @@ for st in "$@"; do
       [ $rc -eq 0 ] || { grep -E "FAIL|Error|error" $O/pt_$TAG.txt | head -30; exit 1; } ;;
     ab)
       IFS=, read -r rounds steps libs <<< "$arg"
-      BA="--warmup 5 --cpu-baseline-seconds 0 --no-bilinear --no-costmap --no-c5 --no-c4 --no-shard --no-cadence"
+      BA="--full --warmup 5 --cpu-baseline-seconds 0 --no-bilinear --no-costmap --no-c5 --no-c4 --no-shard --no-cadence"
       for r in $(seq 1 $rounds); do
         for lib in ${libs//,/ }; do
           if [ "$lib" = "-" ]; then unset MPPI_LIB_PATH; else export MPPI_LIB_PATH=$R/$lib; fi
@@ -40,7 +40,7 @@ for st in "$@"; do
       done
       unset MPPI_LIB_PATH ;;
     bench)
-      timeout -k 10 600 python bench.py ${arg//,/ } > $O/b_$TAG.json 2>$O/b_$TAG.err || { tail -20 $O/b_$TAG.err; exit 1; }
+      timeout -k 10 600 python bench.py --full ${arg//,/ } > $O/b_$TAG.json 2>$O/b_$TAG.err || { tail -20 $O/b_$TAG.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/b_$TAG.json')); c=d['config']; print('value', d['value'], 'sync', c.get('sync_steps_per_s'), 'roll', d['roofline']['kernel_avg_ms'], 'frac', d['roofline']['frac'], 'c4', d.get('c4', {}).get('steps_per_s'), 'shard', (d.get('c4_shard') or {}).get('sharded_ms_per_step'))"
       python3 -c "import json; d=json.load(open('$O/b_$TAG.json')); [print(r) for r in (d.get('cadence') or {}).get('rows', [])]" ;;
     wcal)
@@ -56,7 +56,7 @@ for k,v in d.items(): print(k[:40], 'WRITE_SIZE per launch (KB):', [round(x) for
       grep -E "back-to-back|async_tail|relaunch|server launches" $O/diag_$TAG.txt | head -20 ;;
     prof)
       cd /tmp && export TMPDIR=/tmp
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o k --output-format csv -- python3 $R/bench.py ${arg//,/ } > $O/bp_$TAG.json 2> $O/bp_$TAG.err || { tail -20 $O/bp_$TAG.err; exit 1; }
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o k --output-format csv -- python3 $R/bench.py --full ${arg//,/ } > $O/bp_$TAG.json 2> $O/bp_$TAG.err || { tail -20 $O/bp_$TAG.err; exit 1; }
       cd $R ;;
     pmc)
       GIT_HEAD=$arg bash profiles/pmc.sh $TAG > $O/pmc_$TAG.log 2>&1 || { tail -5 $O/pmc_$TAG.log; cat $O/pmc_$TAG/status.txt; exit 1; }

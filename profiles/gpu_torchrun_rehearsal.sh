@@ -9,6 +9,6 @@ N=${2:-2}
 O=$R/gpurun_out
 cd $R
 MPPI_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --steps 20 --warmup 5 > $O/tr_$TAG.json 2> $O/tr_$TAG.err \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $N --steps 20 --warmup 5 > $O/tr_$TAG.json 2> $O/tr_$TAG.err \
     || { tail -30 $O/tr_$TAG.err; exit 1; }
 cat $O/tr_$TAG.json

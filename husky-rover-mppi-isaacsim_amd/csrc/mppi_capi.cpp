@@ -26,6 +26,7 @@
 #include "mppi_costmap.h"
 #include "mppi_kernels.h"
 #include "mppi_python25d.h"
+#include "mppi_score.h"
 
 using namespace mppi;
 
@@ -224,6 +225,7 @@ struct mppi_ctx {
   double t_roll = 0, t_fin = 0, t_tail = 0;
   int64_t launches = 0, tail_launches = 0;
   Plan last_plan;
+  double score_ms = 0;  // HIP-event time of the last scoring kernel (mppi_get_score_ms)
 };
 
 namespace {
@@ -1783,6 +1785,186 @@ int mppi_dump_rollouts(mppi_ctx* c, float* traj, float* hv, float* lw, float* rw
   for (float* p : dev)
     if (p) hipFree(p);
   return out_rc;
+}
+
+// ---- path scoring (mppi_score.hip) ----
+namespace {
+
+// Score n device-resident paths of `stride` waypoints from `st` (x, y, goal) with the context's
+// costmap and critic parameters; the kernel is bracketed by HIP events (score_ms).  Waits for the stream.
+int score_device(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* lengths, const float* traj,
+                 const float* lw, const float* rw, const float* v, const mppi_state& st, float* cost,
+                 float* terms, int32_t* collisions) {
+  const mppi_params& p = c->p;
+  ServerCmd d;
+  state_fields(p, st, d);
+  ScoreArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.traj = traj;
+  a.lw = lw;
+  a.rw = rw;
+  a.v = v;
+  a.lengths = lengths;
+  a.n = n;
+  a.stride = stride;
+  a.cm = c->cm;
+  a.cm_size = c->cm_size;
+  a.hw = c->cm_hw;
+  a.res_c = c->cm_res;
+  a.gx = d.gx;
+  a.gy = d.gy;
+  a.igx = d.igx;
+  a.igy = d.igy;
+  a.pf_scale = d.pf_scale;
+  a.pf_far = d.pf_far;
+  a.speed_on = d.speed_on;
+  a.vmax = p.v_max_linear;
+  a.thr = p.collision_threshold;
+  a.pen = p.collision_penalty;
+  a.w_path = p.w_path;
+  a.w_slope = p.w_slope;
+  a.w_speed = p.w_speed;
+  a.w_obs = p.w_obstacle;
+  a.cost = cost;
+  a.terms = terms;
+  a.collisions = collisions;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = launch_score(a, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev)
+    if (x) hipEventDestroy(x);
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("score: ") + hipGetErrorString(e));
+  c->score_ms = ms;
+  return MPPI_OK;
+}
+
+size_t up16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+}  // namespace
+
+int mppi_score_paths(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* lengths, const float* traj,
+                     const float* left_wheel, const float* right_wheel, const float* lin_vel,
+                     const mppi_state* origin, mppi_path_scores* out) {
+  if (!c) return fail(MPPI_EINVAL, "null context");
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (!traj || !lin_vel || !out) return fail(MPPI_EINVAL, "score_paths: null traj, lin_vel or out");
+  if (n < 0 || stride < 1) return fail(MPPI_EINVAL, "score_paths: need n >= 0 and stride >= 1");
+  if ((left_wheel == nullptr) != (right_wheel == nullptr))
+    return fail(MPPI_EINVAL, "score_paths: give both wheel arrays or neither");
+  if (n * (int64_t)stride >= ((int64_t)1 << 31)) return fail(MPPI_EINVAL, "score_paths: n * stride must be below 2^31");
+  if (lengths)
+    for (int64_t i = 0; i < n; ++i)
+      if (lengths[i] < 1 || lengths[i] > stride)
+        return fail(MPPI_EINVAL, "score_paths: lengths[" + std::to_string(i) + "] outside [1, stride]");
+  if (!c->cm) return fail(MPPI_ESTATE, "score_paths: no costmap: call mppi_set_costmap first");
+  if (!origin && !c->have_state) return fail(MPPI_ESTATE, "score_paths: no origin and no state set");
+  if (n == 0) return MPPI_OK;
+  const mppi_state st = origin ? *origin : c->st;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const bool wheels = left_wheel != nullptr;
+  const size_t nS = (size_t)n * stride;
+  // one allocation, every array 16-byte aligned: [traj][lw][rw][v][lengths][cost][terms][collisions]
+  const size_t b3 = up16(3 * nS * sizeof(float)), b1 = up16(nS * sizeof(float)), bn = up16((size_t)n * 4);
+  const size_t bytes = b3 * (wheels ? 3 : 1) + b1 + bn * 3 + up16((size_t)n * 16);
+  char* buf = nullptr;
+  HIP_TRY(hipMalloc(&buf, bytes));
+  char* q = buf;
+  float* d_traj = (float*)q;
+  q += b3;
+  float* d_lw = nullptr;
+  float* d_rw = nullptr;
+  if (wheels) {
+    d_lw = (float*)q;
+    q += b3;
+    d_rw = (float*)q;
+    q += b3;
+  }
+  float* d_v = (float*)q;
+  q += b1;
+  int32_t* d_len = (int32_t*)q;
+  q += bn;
+  float* d_cost = (float*)q;
+  q += bn;
+  float* d_terms = (float*)q;
+  q += up16((size_t)n * 16);
+  int32_t* d_col = (int32_t*)q;
+  hipError_t e = hipMemcpyAsync(d_traj, traj, 3 * nS * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && wheels) e = hipMemcpyAsync(d_lw, left_wheel, 3 * nS * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && wheels) e = hipMemcpyAsync(d_rw, right_wheel, 3 * nS * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_v, lin_vel, nS * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && lengths) e = hipMemcpyAsync(d_len, lengths, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+  int rc = MPPI_OK;
+  if (e == hipSuccess)
+    rc = score_device(c, n, stride, lengths ? d_len : nullptr, d_traj, d_lw, d_rw, d_v, st, d_cost, d_terms, d_col);
+  if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK) e = hipStreamSynchronize(c->stream);
+  hipFree(buf);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("score_paths: ") + hipGetErrorString(e));
+  return MPPI_OK;
+}
+
+int mppi_get_cost_terms(mppi_ctx* c, float* terms, int32_t* collisions) {
+  if (!c) return fail(MPPI_EINVAL, "null context");
+  if (int rc_q = quiesce(c)) return rc_q;
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (!c->have_last) return fail(MPPI_ESTATE, "no step to score");
+  const int64_t K = c->p.num_trajectories;
+  const int H = H_of(c);
+  const size_t KH = (size_t)K * H;
+  if (KH == 0) return MPPI_OK;
+  if (KH >= ((size_t)1 << 31)) return fail(MPPI_EINVAL, "cost_terms: K * H must be below 2^31");
+  // device-side dump buffers for traj, lw, rw, v only, and the 20 bytes per trajectory that leave
+  float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  const size_t cnt[4] = {3 * KH, 3 * KH, 3 * KH, KH};
+  float* d_terms = nullptr;
+  int32_t* d_col = nullptr;
+  int out_rc = MPPI_OK;
+  for (int i = 0; i < 4 && out_rc == MPPI_OK; ++i)
+    if (hipMalloc(&dev[i], cnt[i] * sizeof(float)) != hipSuccess) out_rc = fail(MPPI_EHIP, "cost_terms allocation failed");
+  if (out_rc == MPPI_OK && (hipMalloc(&d_terms, (size_t)K * 16) != hipSuccess || hipMalloc(&d_col, (size_t)K * 4) != hipSuccess))
+    out_rc = fail(MPPI_EHIP, "cost_terms allocation failed");
+  if (out_rc == MPPI_OK) {
+    RolloutArgs d;
+    std::memset(&d, 0, sizeof(d));
+    d.d_traj = dev[0];
+    d.d_lw = dev[1];
+    d.d_rw = dev[2];
+    d.d_v = dev[3];
+    // re-run the last step (deterministic: costs/records are rewritten with identical values)
+    out_rc = enqueue_rollout(c, c->last_proj, c->last_step, c->last_mode, c->last_plan,
+                             c->u_nom[c->last_nominal], c->last_state, &d);
+    if (out_rc == MPPI_OK)
+      out_rc = score_device(c, K, H, nullptr, dev[0], dev[1], dev[2], dev[3], c->last_state, nullptr, d_terms, d_col);
+    if (out_rc == MPPI_OK && terms &&
+        hipMemcpyAsync(terms, d_terms, (size_t)K * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+      out_rc = fail(MPPI_EHIP, "cost_terms copy failed");
+    if (out_rc == MPPI_OK && collisions &&
+        hipMemcpyAsync(collisions, d_col, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+      out_rc = fail(MPPI_EHIP, "cost_terms copy failed");
+    if (out_rc == MPPI_OK && hipStreamSynchronize(c->stream) != hipSuccess) out_rc = fail(MPPI_EHIP, "cost_terms sync failed");
+  }
+  for (float* p : dev)
+    if (p) hipFree(p);
+  if (d_terms) hipFree(d_terms);
+  if (d_col) hipFree(d_col);
+  return out_rc;
+}
+
+int mppi_get_score_ms(mppi_ctx* c, double* ms) {
+  if (!c || !ms) return fail(MPPI_EINVAL, "null argument");
+  *ms = c->score_ms;
+  return MPPI_OK;
 }
 
 int mppi_set_option(mppi_ctx* c, const char* name, int64_t value) {

@@ -1,0 +1,45 @@
+// Scoring of caller-supplied paths with the four critics of critics_warp.py:85-329
+// (oracle/mppi_ref.py critics), see mppi_score.hip.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mppi {
+
+// The kernel's tile: SCORE_PATHS paths per 256-thread workgroup, staged SCORE_CHUNK waypoints at a time.
+// Chunk 12 keeps the workgroup's LDS at 33 KB, four workgroups per CU: the 1024 workgroups of the
+// step-shaped call (n = 65 536) are then one round on 256 CUs.  Measured at that shape: chunk 16
+// (43 KB, three per CU, a second round one third full) 0.126 ms, 12: 0.090 ms, 8: 0.100 ms
+// (profiles/score_paths.json).
+constexpr int SCORE_PATHS = 64;
+constexpr int SCORE_CHUNK = 12;
+constexpr int SCORE_THREADS = 256;
+
+struct ScoreArgs {
+  // paths, trajectory-major (device memory)
+  const float* traj;       // [n][stride][3]
+  const float* lw;         // [n][stride][3] or null (then rw is null too: the slope critic reads traj)
+  const float* rw;
+  const float* v;          // [n][stride]
+  const int32_t* lengths;  // [n], each in [1, stride], or null (every path has stride waypoints)
+  int64_t n;
+  int stride;              // n * stride < 2^31
+  // costmap (critics_warp.py:244-248)
+  const float* cm;
+  int cm_size;
+  float hw, res_c;
+  // goal terms precomputed in float32 in the reference's order (state_fields in mppi_capi.cpp)
+  float gx, gy, igx, igy, pf_scale;
+  int pf_far, speed_on;
+  float vmax, thr, pen;
+  float w_path, w_slope, w_speed, w_obs;
+  // outputs (device memory; any may be null)
+  float* cost;          // [n]
+  float* terms;         // [n][4] path, slope, speed, obstacle (16-byte aligned)
+  int32_t* collisions;  // [n]
+};
+
+hipError_t launch_score(const ScoreArgs& a, hipStream_t st);
+
+}  // namespace mppi

@@ -1,0 +1,263 @@
+// Scoring of caller-supplied paths: the four critics of critics_warp.py:85-329 (oracle/mppi_ref.py
+// critics) applied to paths the engine did not just roll out: logged closed-loop runs
+// (evaluate_trajectory.py), the chosen plan (MPPI_isaac.py:726-752), or a step's own rollouts when the
+// per-critic terms are wanted (mppi_get_cost_terms).  Every op is float32 in the reference's order;
+// each critic's sum is one sequential chain in t (no reduction across t), so the values are the bits
+// the rollout kernels' cost wave produces for the same points.
+//
+// Shape.  A path's row is stride * 12 bytes per array, so one lane per path reading global memory
+// would touch a new cache line with every lane.  Instead a workgroup of 4 waves owns SCORE_PATHS = 64
+// paths and walks them SCORE_CHUNK = 12 waypoints at a time:
+//   load   all 256 threads run along the paths' contiguous floats (a chunk of one path is 144
+//          contiguous bytes of traj / lw / rw and 48 of v), 16 bytes per lane when the rows are
+//          16-byte aligned (stride % 4 == 0), else 4; the chunk after the one being scored is in
+//          flight in registers while the critics run;
+//   stage  the chunk goes to LDS as [path][3 * 12 + 1] (v: [path][12 + 1]) floats: the odd row
+//          stride puts the 32 lanes of a ds_read_b32 group, which read the same waypoint of 32
+//          different paths, on 32 different banks;
+//   score  lane = path, wave = critic: wave 0 extends the path-follow chain, wave 1 the slope chain
+//          (it carries the previous even waypoint across chunks), wave 2 the speed chain, wave 3 the
+//          obstacle chain with its costmap gather and the collision count.  The four chains are
+//          independent, so splitting them over waves keeps every chain's order and keeps all four
+//          SIMDs busy with 64 paths per workgroup.
+// The chunk loop runs to the longest path of the tile, whatever the stride: LDS use does not depend
+// on the path length.  Rows past a path's length are staged but never enter a chain.
+#include "mppi_score.h"
+
+namespace mppi {
+
+namespace {
+
+constexpr int TP = SCORE_PATHS, CT = SCORE_CHUNK, NT = SCORE_THREADS;
+constexpr int ROW3 = 3 * CT + 1;  // floats per path of a staged [t][3] chunk (odd: see above)
+constexpr int ROWV = CT + 1;
+static_assert(NT == 4 * 64 && TP == 64, "one wave per critic, one lane per path");
+static_assert(CT % 4 == 0, "a chunk is whole 16-byte vectors of v and of the [t][3] arrays, and starts on an even t");
+
+struct Smem {
+  float a[3][TP * ROW3];  // traj, lw, rw
+  float v[TP * ROWV];
+  float term[4][TP];
+  int col[TP];
+};
+
+// The registers that hold the chunk in flight: a thread's share of the tile's vectors of VEC floats
+// (C floats per waypoint), rounded up to whole vectors.
+constexpr int stage_floats(int C, int VEC) { return (TP * CT * C / VEC + NT - 1) / NT * VEC; }
+template <int VEC>
+struct Stage {
+  float a[3][stage_floats(3, VEC)];
+  float v[stage_floats(1, VEC)];
+};
+
+// One array's share of a chunk: C floats per waypoint, `len` waypoints from t0 of paths p0 .. p0 + TP - 1.
+// Vector j of the tile = VEC floats at offset (j % spv) * VEC of path j / spv, spv = C * len / VEC.
+template <int VEC, int C, int NF, bool STORE>
+__device__ __forceinline__ void stage_array(const float* __restrict__ g, float (&r)[NF], float* s, int row,
+                                            int64_t p0, int64_t n, int stride, int t0, int len, int tid) {
+  constexpr int NV = NF / VEC;
+  constexpr int SPV_FULL = C * CT / VEC;
+  const bool full = len == CT;
+  const int spv = full ? SPV_FULL : C * len / VEC;
+  const int total = TP * spv;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int j = tid + i * NT;
+    if (j >= total) continue;
+    const int pp = full ? j / SPV_FULL : j / spv;
+    const int o = (j - pp * spv) * VEC;
+    if (p0 + pp >= n) continue;
+    if constexpr (!STORE) {
+      const float* src = g + ((size_t)(p0 + pp) * (size_t)stride + (size_t)t0) * C + o;
+      if constexpr (VEC == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(src);
+        r[4 * i] = q.x;
+        r[4 * i + 1] = q.y;
+        r[4 * i + 2] = q.z;
+        r[4 * i + 3] = q.w;
+      } else {
+        r[i] = *src;
+      }
+    } else {
+      float* dst = s + pp * row + o;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) dst[k] = r[VEC * i + k];
+    }
+  }
+}
+
+template <int VEC, bool WHEELS, bool STORE>
+__device__ __forceinline__ void stage_chunk(const ScoreArgs& a, Stage<VEC>& r, Smem& sm, int64_t p0, int t0, int len,
+                                            int tid) {
+  stage_array<VEC, 3, stage_floats(3, VEC), STORE>(a.traj, r.a[0], sm.a[0], ROW3, p0, a.n, a.stride, t0, len, tid);
+  if constexpr (WHEELS) {
+    stage_array<VEC, 3, stage_floats(3, VEC), STORE>(a.lw, r.a[1], sm.a[1], ROW3, p0, a.n, a.stride, t0, len, tid);
+    stage_array<VEC, 3, stage_floats(3, VEC), STORE>(a.rw, r.a[2], sm.a[2], ROW3, p0, a.n, a.stride, t0, len, tid);
+  }
+  stage_array<VEC, 1, stage_floats(1, VEC), STORE>(a.v, r.v, sm.v, ROWV, p0, a.n, a.stride, t0, len, tid);
+}
+
+// critics_warp.py:190-218: (1 + 5 |dz / (d + 1e-6)|)^2 between waypoints t and t + 2 of one wheel.
+__device__ __forceinline__ float slope_one(const float (&p)[3], const float (&c)[3]) {
+  const float dz = c[2] - p[2];
+  const float dx = c[0] - p[0], dy = c[1] - p[1];
+  const float d = sqrtf(dx * dx + dy * dy);
+  const float ratio = fabsf(dz / (d + 1e-6f));
+  const float s = 1.0f + 5.0f * ratio;
+  return s * s;
+}
+
+// critics_warp.py:244-248 (oracle costmap_at): clamp(trunc(clamp(f, -1, size)), 0, size - 1) is
+// trunc(clamp(f, 0, size - 1)); a NaN coordinate indexes cell 0, as the oracle's fmax / fmin.
+__device__ __forceinline__ int cm_index(const ScoreArgs& a, float x, float y) {
+  const float fx = (x + a.hw) / a.res_c;
+  const float fy = ((-y) + a.hw) / a.res_c;
+  const float top = (float)(a.cm_size - 1);
+  const int ix = (int)fminf(fmaxf(fx, 0.0f), top);
+  const int iy = (int)fminf(fmaxf(fy, 0.0f), top);
+  return ix + a.cm_size * iy;
+}
+
+template <int VEC, bool WHEELS>
+__global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
+  __shared__ Smem sm;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int role = tid >> 6;  // wave-uniform: 0 path, 1 slope, 2 speed, 3 obstacle
+  const int64_t p0 = (int64_t)blockIdx.x * TP;
+  const int64_t p = p0 + lane;
+  const int L = p < a.n ? (a.lengths ? min(a.lengths[p], a.stride) : a.stride) : 0;
+  int Lmax = L;  // the tile's longest path: the same value in every wave
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) Lmax = max(Lmax, __shfl_xor(Lmax, o, 64));
+  Lmax = min(Lmax, a.stride);
+  // staged waypoints: whole 16-byte vectors (stride % 4 == 0 there, so still within the rows)
+  const int Lld = VEC == 4 ? (Lmax + 3) & ~3 : Lmax;
+
+  float acc = 0.0f;  // this wave's chain
+  int col = 0;
+  float pl[3] = {0.0f, 0.0f, 0.0f}, pr[3] = {0.0f, 0.0f, 0.0f};  // slope: the previous even waypoint
+
+  Stage<VEC> r;
+  stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, 0, min(CT, Lld), tid);
+  stage_chunk<VEC, WHEELS, true>(a, r, sm, p0, 0, min(CT, Lld), tid);
+  __syncthreads();
+  for (int t0 = 0; t0 < Lld; t0 += CT) {
+    const int len = min(CT, Lld - t0);
+    const int t1 = t0 + CT;
+    const int len1 = min(CT, Lld - t1);  // <= 0: no next chunk
+    if (len1 > 0) stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, t1, len1, tid);
+
+    const int te = min(t0 + len, L);  // this lane's waypoints of the chunk: [t0, te)
+    if (role == 0) {
+      const float* q = sm.a[0] + lane * ROW3;
+      if (a.pf_far) {  // critics_warp.py:111-119: the terminal waypoint against the intermediate goal
+        const int tl = L - 1;
+        if (tl >= t0 && tl < te) {
+          const float dx = q[3 * (tl - t0)] - a.igx;
+          const float dy = q[3 * (tl - t0) + 1] - a.igy;
+          acc = (dx * dx + dy * dy) * a.pf_scale;
+        }
+      } else {  // :120-123
+        const int tp = min(te, L - 1);
+        for (int t = t0; t < tp; ++t)
+          acc = acc + 10.0f * (fabsf(q[3 * (t - t0)] - a.gx) + fabsf(q[3 * (t - t0) + 1] - a.gy));
+      }
+    } else if (role == 1) {
+      const float* ql = sm.a[WHEELS ? 1 : 0] + lane * ROW3;
+      const float* qr = sm.a[WHEELS ? 2 : 0] + lane * ROW3;
+      for (int s = t0; s < te; s += 2) {  // t0 is even: s runs over the even waypoints
+        const int k = 3 * (s - t0);
+        const float cl[3] = {ql[k], ql[k + 1], ql[k + 2]};
+        float cr[3] = {0.0f, 0.0f, 0.0f};
+        if constexpr (WHEELS) {
+          cr[0] = qr[k];
+          cr[1] = qr[k + 1];
+          cr[2] = qr[k + 2];
+        }
+        if (s >= 2 && s <= L - 2) {  // the term of t = s - 2 < L - 3
+          float term = slope_one(pl, cl);
+          if constexpr (WHEELS) {
+            const float rs = slope_one(pr, cr);
+            term = (term > rs) ? term : rs;
+          }
+          acc = acc + term;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          pl[i] = cl[i];
+          pr[i] = cr[i];
+        }
+      }
+    } else if (role == 2) {
+      if (a.speed_on) {  // critics_warp.py:281-300
+        const float* q = sm.v + lane * ROWV;
+        for (int t = t0; t < te; ++t) {
+          const float vt = q[t - t0];
+          acc = acc + (a.vmax - vt) / (vt + 0.0001f);
+        }
+      }
+    } else {
+      const float* q = sm.a[0] + lane * ROW3;
+      for (int t = t0; t < te; ++t) {  // critics_warp.py:244-262
+        const float c = a.cm[cm_index(a, q[3 * (t - t0)], q[3 * (t - t0) + 1])];
+        if (c > a.thr) {
+          acc = acc + a.pen;
+          ++col;
+        }
+        acc = acc + c;
+      }
+    }
+    __syncthreads();  // every wave is done with the staged chunk
+    if (len1 > 0) {
+      stage_chunk<VEC, WHEELS, true>(a, r, sm, p0, t1, len1, tid);
+      __syncthreads();
+    }
+  }
+
+  sm.term[role][lane] = acc;
+  if (role == 3) sm.col[lane] = col;
+  __syncthreads();
+  if (role == 0 && p < a.n) {
+    const float pf = sm.term[0][lane], sw = sm.term[1][lane], sp = sm.term[2][lane], ob = sm.term[3][lane];
+    if (a.terms) *reinterpret_cast<float4*>(a.terms + 4 * (size_t)p) = make_float4(pf, sw, sp, ob);
+    if (a.cost) {  // critics_warp.py:325-329
+      float cost = a.w_path * pf;
+      cost = cost + a.w_slope * sw;
+      cost = cost + a.w_speed * sp;
+      cost = cost + a.w_obs * ob;
+      a.cost[p] = cost;
+    }
+    if (a.collisions) a.collisions[p] = sm.col[lane];
+  }
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+hipError_t launch_score(const ScoreArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!a.traj || !a.v || !a.cm || a.stride < 1 || a.cm_size < 1 || (a.lw == nullptr) != (a.rw == nullptr) ||
+      (a.terms && !aligned16(a.terms)) || a.n * (int64_t)a.stride >= ((int64_t)1 << 31))
+    return hipErrorInvalidValue;
+  const unsigned blocks = (unsigned)((a.n + TP - 1) / TP);
+  const bool wheels = a.lw != nullptr;
+  // 16-byte loads when every row of every array starts 16-byte aligned
+  const bool wide = a.stride % 4 == 0 && aligned16(a.traj) && aligned16(a.v) &&
+                    (!wheels || (aligned16(a.lw) && aligned16(a.rw)));
+  if (wide) {
+    if (wheels)
+      hipLaunchKernelGGL((mppi_score_kernel<4, true>), dim3(blocks), dim3(NT), 0, st, a);
+    else
+      hipLaunchKernelGGL((mppi_score_kernel<4, false>), dim3(blocks), dim3(NT), 0, st, a);
+  } else {
+    if (wheels)
+      hipLaunchKernelGGL((mppi_score_kernel<1, true>), dim3(blocks), dim3(NT), 0, st, a);
+    else
+      hipLaunchKernelGGL((mppi_score_kernel<1, false>), dim3(blocks), dim3(NT), 0, st, a);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace mppi

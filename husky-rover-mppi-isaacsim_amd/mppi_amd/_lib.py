@@ -62,6 +62,14 @@ class MppiOutputs(C.Structure):
                                    "heading_sim", "left_wheel_sim", "right_wheel_sim")]
 
 
+class MppiPathScores(C.Structure):
+    """mppi_path_scores: host output pointers of mppi_score_paths (any may be NULL)."""
+    _fields_ = [("cost", _FP), ("terms", _FP), ("collisions", C.POINTER(C.c_int32))]
+
+
+COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
+
+
 # name -> (restype, argtypes); must match include/mppi.h (tests/test_lib_symbols.py checks both ways)
 _PROTOS = {
     "mppi_abi_version": (C.c_int, []),
@@ -86,6 +94,10 @@ _PROTOS = {
     "mppi_step_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MppiOutputs)]),
     "mppi_get_costs": (C.c_int, [C.c_void_p, _FP, C.c_int64]),
     "mppi_dump_rollouts": (C.c_int, [C.c_void_p] + [_FP] * 8),
+    "mppi_score_paths": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _FP, _FP, _FP, _FP,
+                                   C.POINTER(MppiState), C.POINTER(MppiPathScores)]),
+    "mppi_get_cost_terms": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32)]),
+    "mppi_get_score_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_set_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "mppi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "mppi_get_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -259,6 +271,45 @@ def make_state(x, y, heading=(1.0, 0.0, 0.0), left_wheel_speed=0.0, right_wheel_
     s.goal_x, s.goal_y = float(goal_x), float(goal_y)
     s.std_dev_u1, s.std_dev_u2 = float(std_dev_u1), float(std_dev_u2)
     return s
+
+
+def check_paths(traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None):
+    """Validate and normalise the arrays of Engine.score_paths (no library call).
+
+    traj [n, L, 3], lin_vel [n, L], optional left_wheel / right_wheel [n, L, 3] (both or neither),
+    optional lengths [n] of integers in [1, L].  Returns (n, L, traj, lin_vel, left_wheel,
+    right_wheel, lengths) as C-contiguous float32 / int32 arrays (None where not given); raises
+    ValueError on anything the library would refuse.
+    """
+    traj = np.ascontiguousarray(traj, dtype=np.float32)
+    if traj.ndim != 3 or traj.shape[2] != 3:
+        raise ValueError(f"traj must have shape [n, L, 3], got {traj.shape}")
+    n, L = int(traj.shape[0]), int(traj.shape[1])
+    if L < 1:
+        raise ValueError("paths need at least one waypoint")
+    if n * L >= 2 ** 31:
+        raise ValueError("n * L must be below 2^31")
+    lin_vel = np.ascontiguousarray(lin_vel, dtype=np.float32)
+    if lin_vel.shape != (n, L):
+        raise ValueError(f"lin_vel must have shape {(n, L)}, got {lin_vel.shape}")
+    if (left_wheel is None) != (right_wheel is None):
+        raise ValueError("give both wheel arrays or neither")
+    if left_wheel is not None:
+        left_wheel = np.ascontiguousarray(left_wheel, dtype=np.float32)
+        right_wheel = np.ascontiguousarray(right_wheel, dtype=np.float32)
+        for name, a in (("left_wheel", left_wheel), ("right_wheel", right_wheel)):
+            if a.shape != (n, L, 3):
+                raise ValueError(f"{name} must have shape {(n, L, 3)}, got {a.shape}")
+    if lengths is not None:
+        raw = np.asarray(lengths)
+        if raw.shape != (n,):
+            raise ValueError(f"lengths must have shape {(n,)}, got {raw.shape}")
+        if raw.dtype.kind not in "iu":
+            raise ValueError("lengths must be integers")
+        if n and (raw.min() < 1 or raw.max() > L):
+            raise ValueError(f"lengths must lie in [1, {L}]")
+        lengths = np.ascontiguousarray(raw, dtype=np.int32)
+    return n, L, traj, lin_vel, left_wheel, right_wheel, lengths
 
 
 class Engine:
@@ -447,6 +498,39 @@ class Engine:
                 "mppi_dump_rollouts")
         return arrs
 
+    def score_paths(self, traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None, state=None):
+        """mppi_score_paths: the critics on caller-supplied paths, traj [n, L, 3], lin_vel [n, L].
+
+        Without wheel arrays the slope critic runs on the body path; lengths [n] gives ragged paths
+        (rows past a path's length are not read); state (MppiState) is the position and goal the
+        critics measure from, default the engine's current state.  Returns dict(cost [n],
+        terms [n, 4] in COST_TERMS order, collisions [n])."""
+        n, L, traj, lin_vel, left_wheel, right_wheel, lengths = check_paths(traj, lin_vel, left_wheel,
+                                                                           right_wheel, lengths)
+        out = dict(cost=np.zeros(n, np.float32), terms=np.zeros((n, 4), np.float32),
+                   collisions=np.zeros(n, np.int32))
+        i32 = C.POINTER(C.c_int32)
+        sc = MppiPathScores(_fp(out["cost"]), _fp(out["terms"]), out["collisions"].ctypes.data_as(i32))
+        self._c(self.lib.mppi_score_paths(
+            self.ctx, n, L, None if lengths is None else lengths.ctypes.data_as(i32), _fp(traj),
+            None if left_wheel is None else _fp(left_wheel), None if right_wheel is None else _fp(right_wheel),
+            _fp(lin_vel), None if state is None else C.byref(state), C.byref(sc)), "mppi_score_paths")
+        return out
+
+    def cost_terms(self):
+        """mppi_get_cost_terms: (terms [K, 4] in COST_TERMS order, collisions [K]) of the last step's rollouts."""
+        terms = np.zeros((self.K, 4), np.float32)
+        col = np.zeros(self.K, np.int32)
+        self._c(self.lib.mppi_get_cost_terms(self.ctx, _fp(terms), col.ctypes.data_as(C.POINTER(C.c_int32))),
+                "mppi_get_cost_terms")
+        return terms, col
+
+    def score_ms(self):
+        """HIP-event time (ms) of the last scoring kernel (score_paths / cost_terms)."""
+        ms = C.c_double()
+        self._c(self.lib.mppi_get_score_ms(self.ctx, C.byref(ms)), "mppi_get_score_ms")
+        return ms.value
+
     def set_option(self, name, value):
         """mppi_set_option (include/mppi.h): per-context tuning / test hooks by name."""
         self._c(self.lib.mppi_set_option(self.ctx, name.encode(), int(value)), "mppi_set_option")
@@ -612,6 +696,13 @@ class Group:
     def costs(self):
         """Every trajectory's cost in global order (the members' shards concatenated)."""
         return np.concatenate([m.costs()[:self.shard(i)[1]] for i, m in enumerate(self.members)])
+
+    def cost_terms(self):
+        """Every trajectory's critic terms [K, 4] and collision count [K] in global order."""
+        parts = [m.cost_terms() for m in self.members]
+        counts = [self.shard(i)[1] for i in range(len(self.members))]
+        return (np.concatenate([t[:c] for (t, _), c in zip(parts, counts)]),
+                np.concatenate([k[:c] for (_, k), c in zip(parts, counts)]))
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

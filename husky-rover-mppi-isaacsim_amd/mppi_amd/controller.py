@@ -261,6 +261,7 @@ class MPPI_Controller:
                          traj_sim=z3, heading_sim=z3.copy(), left_wheel_sim=z3.copy(),
                          right_wheel_sim=z3.copy())
         self._dump = None
+        self._cost_terms = None
         o = self._out
         self.optimal_u1_wp = EngineArray(lambda: self.engine.get_nominal()[0],
                                          lambda v: self._set_nominal(v, None), "optimal_u1_wp")
@@ -274,6 +275,10 @@ class MPPI_Controller:
         self.right_wheel_pos_sim = EngineArray(lambda: self._sim("right_wheel_sim"), name="right_wheel_pos_sim")
         self.costs_wp = EngineArray(self._costs, name="costs_wp")
         self.weights_wp = EngineArray(self._weights, name="weights_wp")
+        # the four unweighted critic values of every rollout of the last step ([K, 4] in
+        # _lib.COST_TERMS order) and its waypoints in collision ([K])
+        self.cost_terms_wp = EngineArray(lambda: self._terms()[0], name="cost_terms_wp")
+        self.collisions_wp = EngineArray(lambda: self._terms()[1], name="collisions_wp")
         self.costmap_wp = EngineArray(lambda: np.asarray(self.surface.costmap, np.float32).ravel(),
                                       self._assign_costmap, "costmap_wp")
         for name, key, shape3 in (("trajectories", "traj", True), ("heading_vectors", "hv", True),
@@ -376,6 +381,31 @@ class MPPI_Controller:
         c = self.engine.costs().astype(np.float64)
         return np.exp(-(c - c.min()) / self.temperature).astype(np.float32)
 
+    def _terms(self):
+        """(terms [K, 4], collisions [K]) of the last step, fetched once per step."""
+        if self._cost_terms is None:
+            self._cost_terms = self.engine.cost_terms()
+        return self._cost_terms
+
+    def score_paths(self, traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None, state=None):
+        """The critics on caller-supplied paths (Engine.score_paths): logged runs
+        (evaluate_trajectory.py) or any candidate plan, with this controller's costmap, weights and
+        horizon; state defaults to the pose and goal of the last reset / step."""
+        if self.engine is None:
+            raise RuntimeError("call warp_setup() first")
+        return self.engine.score_paths(traj, lin_vel, left_wheel, right_wheel, lengths, state)
+
+    def optimal_cost(self):
+        """Cost of the chosen plan (MPPI_isaac.py:726-752): the last step's optimal rollout
+        (trajectories_sim, the wheel paths, optimal_lin_vel_wp) scored from the current robot pose.
+        Waits for a deferred optimal rollout.  Returns (cost, terms [4])."""
+        if self.engine is None:
+            raise RuntimeError("call warp_setup() first")
+        traj = self._sim("traj_sim")   # (first: it refreshes every *_sim array)
+        r = self.engine.score_paths(traj[None], self._out["lin_vel"][None], self._out["left_wheel_sim"][None],
+                                    self._out["right_wheel_sim"][None], state=self._state())
+        return float(r["cost"][0]), r["terms"][0].copy()
+
     def _dumped(self, key, n, vec3):
         def get():
             if self._dump is None:
@@ -410,6 +440,7 @@ class MPPI_Controller:
         self._out = self.engine.step(proj, self.step_index)
         self._tail_fresh = not self.async_tail
         self._dump = None
+        self._cost_terms = None
         self.step_index += 1
 
     # aliases requested by the drop-in contract

@@ -269,6 +269,41 @@ int mppi_get_costs(mppi_ctx* ctx, float* costs_host, int64_t n);
 int mppi_dump_rollouts(mppi_ctx* ctx, float* traj, float* heading, float* left_wheel,
                        float* right_wheel, float* lin_vel, float* ang_vel, float* u1, float* u2);
 
+/* ---- path scoring and per-critic terms ----
+ * _evaluate_trajectories_kernel (critics_warp.py:302-329) on paths the caller supplies: the
+ * offline re-scoring of logged runs (evaluate_trajectory.py, dim = 1, paths of up to 3500
+ * waypoints) and the cost of the chosen plan (MPPI_isaac.py:726-752).  Besides the weighted
+ * total the four critic values are returned unweighted (the thesis compared critics by
+ * commenting lines :325-329 in and out), and the number of waypoints in collision. */
+enum mppi_cost_term { MPPI_TERM_PATH = 0, MPPI_TERM_SLOPE = 1, MPPI_TERM_SPEED = 2, MPPI_TERM_OBSTACLE = 3 };
+typedef struct mppi_path_scores { /* host pointers, any may be NULL */
+  float* cost;         /* [n]   weighted total, as costs_wp                                  */
+  float* terms;        /* [n*4] unweighted critic values, mppi_cost_term order               */
+  int32_t* collisions; /* [n]   waypoints with costmap > collision_threshold                 */
+} mppi_path_scores;
+
+/* Scores n paths of up to `stride` waypoints, trajectory-major like the dump arrays (host memory,
+ * copied in and out): traj, left_wheel, right_wheel [n*stride*3], lin_vel [n*stride]; lengths [n]
+ * (each in [1, stride]; NULL: every path has stride waypoints; rows past a path's length are not
+ * read).  left_wheel and right_wheel are both given or both NULL; with NULL the slope critic runs
+ * on the body path (_avoid_slope, critics_warp.py:131-166: the wheel form with both wheels on
+ * traj).  origin: the robot position and goal the critics measure from (x, y, goal_x, goal_y; the
+ * other fields are not read), NULL = the context's current state.  Weights, horizon (it does not
+ * depend on stride), thresholds and v_max_linear are the context's params, the costmap the
+ * context's.  Needs a costmap (MPPI_ESTATE otherwise), no DEM.  n * stride < 2^31.  Synchronous;
+ * changes no state of the context. */
+int mppi_score_paths(mppi_ctx* ctx, int64_t n, int32_t stride, const int32_t* lengths,
+                     const float* traj, const float* left_wheel, const float* right_wheel,
+                     const float* lin_vel, const mppi_state* origin, mppi_path_scores* out);
+/* The critic terms [K*4] and collision counts [K] of the last step's K rollouts of this context
+ * (either may be NULL): re-runs the step like mppi_dump_rollouts with the dump buffers kept on
+ * the device, scores them there and copies out 20 bytes per trajectory.  terms recombined as
+ * critics_warp.py:325-329 (w_path * path, += w_slope * slope, += w_speed * speed,
+ * += w_obstacle * obstacle) are the bits of mppi_get_costs. */
+int mppi_get_cost_terms(mppi_ctx* ctx, float* terms, int32_t* collisions);
+/* HIP-event time of the last scoring kernel of the context, in milliseconds. */
+int mppi_get_score_ms(mppi_ctx* ctx, double* ms);
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

@@ -129,14 +129,14 @@ struct mppi_ctx {
   // Resident step server (mppi_step_server_kernel): sampled steps of the role-split plan run on one
   // resident launch that polls the command block `cmd` (pinned) instead of one launch per step
   // (mppi_set_option "resident", env MPPI_RESIDENT).  It exits after srv_idle_us without a command, on
-  // cmd->stop == its launch id (every other call on the context stops it first: quiesce) or on a
+  // the command's stop slot == its launch id (every other call on the context stops it first: quiesce) or on a
   // failed step.  resident 1 (default): only back-to-back calls (within half the idle limit of the
   // last step's return) keep or start it, a step after a longer gap runs as separate launches (the
   // caller's frame cadence: a launch of the server per frame costs more than the launches it saves);
   // 2: every step whose plan fits; 0: never.
   int resident = 1;
-  ServerCmd* cmd = nullptr;   // pinned
-  unsigned* relay = nullptr;  // device [64]: workgroup 0's relay of the command (ServerArgs::relay)
+  ServerCmdWire* cmd = nullptr;         // pinned: the command's tagged slots (mppi_cmd.h)
+  unsigned long long* relay = nullptr;  // device [kCmdSlots]: the head's relay of them (ServerArgs::relay)
   bool srv_running = false;
   bool srv_exiting = false;   // a stop was posted and the launch may not have retired yet
   unsigned srv_launch_id = 0;  // the running (or last) launch's id: its stop word
@@ -571,11 +571,11 @@ int sync_tail(mppi_ctx* c) {
   return MPPI_OK;
 }
 
-// Tell the running server to leave (it finishes the step it runs, reads its launch id in cmd->stop
+// Tell the running server to leave (it finishes the step it runs, reads its launch id in the command's stop slot
 // and exits) without waiting: launches enqueued after it on the context stream run once it retired.
 void post_stop(mppi_ctx* c) {
   if (!c->srv_running) return;
-  __atomic_store_n(&c->cmd->stop, c->srv_launch_id, __ATOMIC_RELEASE);
+  __atomic_store_n(&c->cmd->slot[kCmdStopSlot], (uint64_t)c->srv_launch_id, __ATOMIC_RELEASE);
   c->srv_running = false;
   c->srv_exiting = true;
 }
@@ -610,7 +610,7 @@ void rearm_counters(mppi_ctx* c) {
 }
 
 // Launch the resident server for the posted command `seq` (its first), with the plan of the last
-// server_step (c->srv_pl ...).  Neither the relay nor cmd->stop needs a reset: the relay's seq word is
+// server_step (c->srv_pl ...).  Neither the relay nor the stop slot needs a reset: the relay's tags are
 // older than this command, and the stop words hold an earlier launch's id, never this one's (a
 // relaunch for the same command included).
 int launch_server(mppi_ctx* c, unsigned seq) {
@@ -1140,8 +1140,7 @@ int server_step(mppi_ctx* c, int proj, uint64_t step, const Plan& pl, int P, int
   trace_mark(c, 2);
   const unsigned seq = ++c->seq;
   c->wait_seq = seq;
-  // the command: every field, then seq (release: the server reads the fields after seeing it)
-  ServerCmd* cmd = c->cmd;
+  // the command: every word travels with the step's seq as its tag (cmd_post below)
   ServerCmd d;
   std::memset(&d, 0, sizeof(d));
   state_fields(c->p, c->st, d);
@@ -1159,10 +1158,7 @@ int server_step(mppi_ctx* c, int proj, uint64_t step, const Plan& pl, int P, int
   // the command is posted; a head that leaves anyway (a slower host) never relays the command, and
   // wait_done relaunches the server with it
   if (c->srv_running && now_us() - c->srv_last_us > 0.5 * (double)c->srv_idle_us) post_stop(c);
-  unsigned* cw = reinterpret_cast<unsigned*>(cmd);
-  const unsigned* dw = reinterpret_cast<const unsigned*>(&d);
-  for (int i = 2; i < kCmdWords; ++i) __atomic_store_n(cw + i, dw[i], __ATOMIC_RELAXED);
-  __atomic_store_n(&cmd->seq, seq, __ATOMIC_RELEASE);
+  cmd_post(c->cmd, d, seq);
   c->srv_pl = pl;
   c->srv_P = P;
   c->srv_ncol = ncol;
@@ -1421,8 +1417,8 @@ int mppi_create(const mppi_params* params, int32_t device, mppi_ctx** out) {
       hipMalloc(&c->cdiv_bad, sizeof(unsigned)) != hipSuccess ||
       hipMalloc(&c->level1_cnt, 128) != hipSuccess ||  // [0]: finish handoff, [16]: the server's record count
       hipMalloc(&c->uopt, (size_t)2 * H * sizeof(unsigned long long)) != hipSuccess ||
-      hipHostMalloc(&c->cmd, sizeof(ServerCmd), hipHostMallocDefault) != hipSuccess ||
-      hipMalloc(&c->relay, 64 * sizeof(unsigned)) != hipSuccess ||
+      hipHostMalloc(&c->cmd, sizeof(ServerCmdWire), hipHostMallocDefault) != hipSuccess ||
+      hipMalloc(&c->relay, sizeof(ServerCmdWire)) != hipSuccess ||
       hipMalloc(&c->clk, kClkWords * sizeof(uint64_t)) != hipSuccess)
     return cleanup(fail(MPPI_EHIP, "device allocation failed"));
   for (int i = 0; i < kTailSlots; ++i)
@@ -1433,7 +1429,7 @@ int mppi_create(const mppi_params* params, int32_t device, mppi_ctx** out) {
   if (hipMemset(c->u_nom[0], 0, 2 * H * sizeof(float)) != hipSuccess ||
       hipMemset(c->u_nom[1], 0, 2 * H * sizeof(float)) != hipSuccess ||
       hipMemset(c->cost, 0, std::max<int64_t>(p.num_trajectories, 1) * sizeof(float)) != hipSuccess ||
-      hipMemset(c->relay, 0, 64 * sizeof(unsigned)) != hipSuccess ||
+      hipMemset(c->relay, 0, sizeof(ServerCmdWire)) != hipSuccess ||
       hipMemset(c->clk, 0, kClkWords * sizeof(uint64_t)) != hipSuccess)
     return cleanup(fail(MPPI_EHIP, "hipMemset failed"));
   for (auto& e : c->ev)
@@ -1451,7 +1447,7 @@ int mppi_create(const mppi_params* params, int32_t device, mppi_ctx** out) {
   c->out_host = new float[16 * H]();
   std::memset(c->stage, 0, 16 * H * sizeof(float));
   *c->done = 0;
-  std::memset(c->cmd, 0, sizeof(ServerCmd));
+  std::memset(c->cmd, 0, sizeof(ServerCmdWire));
   if (hipMemset(c->level1_cnt, 0, 128) != hipSuccess ||
       hipMemset(c->uopt, 0, (size_t)2 * H * sizeof(unsigned long long)) != hipSuccess)
     return cleanup(fail(MPPI_EHIP, "hipMemset failed"));

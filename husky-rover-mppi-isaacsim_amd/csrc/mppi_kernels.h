@@ -4,30 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mppi_cmd.h"
+
 namespace mppi {
 
-// The resident step server's command block (mppi_capi.cpp "resident step server"): pinned host
-// memory the host fills for every step (every field, then seq with release order); the server's
-// workgroups poll seq and read the rest with system-scope loads.  stop == the launch's launch_id
-// ends that launch (a later launch has another id: the host never clears the word).
-struct ServerCmd {
-  unsigned seq;    // the step's completion sequence number (written last)
-  unsigned stop;   // (same 8-byte word as seq: one poll reads both; checked before seq)
-  int eps_slot;    // normals slot of the step
-  int cur;         // nominal buffer the step reads (the finish writes the other one)
-  int tail_slot;   // deferred optimal rollout slot (mode 2)
-  int mode;        // 1: finish with the whole optimal rollout, 2: step 0 only (the rest deferred)
-  int noise_slot;  // >= 0: the rollout workgroups outside the finish generate the normals of Philox block
-                   // base noise_n_base into this slot after their records (-1: none)
-  unsigned noise_n_base_lo;
-  float x0, y0, h0x, h0y, h0z, wl, wr, gx, gy, s1, s2, igx, igy, pf_scale;  // robot / goal state
-  int pf_far, speed_on;
-  unsigned noise_n_base_hi;
-  unsigned pad1[7];
-};
 constexpr int kTailSlots = 4;  // deferred optimal rollouts in flight (mppi_capi.cpp; 8 / 16 measured
                                // within noise, profiles/r04_notes.md)
-constexpr int kCmdWords = 25;                 // the words a step reads (seq .. noise_n_base_hi)
 constexpr unsigned kDoneFail = 0x80000000u;   // done | kDoneFail: the step's finish gave up
 struct FinishArgs {
   int H;
@@ -159,22 +141,22 @@ hipError_t launch_rollout_pair(const RolloutArgs& a, int blocks, size_t lds, hip
 // trajectories; rings [D][4 + 4][TB] + cost[TB] + slope[TB] in LDS.
 constexpr int ROLES_WAVES_PER_TRAJ_WAVE = 4;
 // The resident step server (mppi_step_server_kernel): one workgroup per 256 trajectories of the
-// role-split rollout, resident across steps.  Per step every workgroup waits for cmd->seq to reach
-// the next sequence number (or cmd->stop; the head also leaves after idle_ticks of the 100 MHz
+// role-split rollout, resident across steps.  Per step every workgroup waits for a command tagged with
+// the next sequence number (or the command's stop slot; the head also leaves after idle_ticks of the 100 MHz
 // clock without a command, and the others leave on the stop it relays), runs its rollout and writes its record through, and takes a ticket from rec_cnt;
 // the workgroups holding the last fin_groups tickets run the column-split finish (each after rec_cnt
 // reaches nroll, or wait_ticks: then the step publishes done | kDoneFail); the other workgroups
 // generate the normals of step + 2 meanwhile (ServerCmd::noise_slot, a static share per ticket;
 // workgroup 0's first wave keeps out of it).  Only workgroup
 // 0 polls the pinned command (256 workgroups polling host memory cost ~30 us per step, one ~4 us:
-// profiles/ubench/server.hip); it relays the command words and seq / stop through device memory.
+// profiles/ubench/server.hip); it relays the tagged command slots (mppi_cmd.h) through device memory.
 struct ServerArgs {
   FinishArgs f;
   int nroll, fin_P, fin_ncol, fin_groups;
   unsigned* rec_cnt;          // [0] records counted; zeroed, re-armed by the finish
-  const ServerCmd* cmd;       // pinned host memory (polled by workgroup 0 only)
-  unsigned* relay;            // device: [0] seq, [1] stop (the launch_id of the launch that stopped) as relayed
-                              // by the head, [16, 16 + kCmdWords) the command words
+  const ServerCmdWire* cmd;   // pinned host memory (polled by the head only): the tagged command slots
+  unsigned long long* relay;  // device [kCmdSlots]: the same slots as relayed by the head, slot kCmdStopSlot
+                              // the launch_id of the launch it stopped
   unsigned launch_id;         // unique per launch of the context (never 0): the stop word that ends it
   float* eps[3];              // the normals slots
   float* u_nom[2];            // the nominal double buffer, [2H] each

@@ -3410,12 +3410,14 @@ __global__ __launch_bounds__(256) void mppi_noise_kernel(uint64_t seed, uint64_t
 
 // =====================================================================  resident step server
 // One launch serves a sequence of sampled steps (mppi_capi.cpp "resident step server"): workgroup b
-// is rollout block b of every step.  Per step: the head's wave 0 polls cmd->seq (one lane, system
-// scope) until it reaches `expect` (or cmd->stop, or idle_ticks without a command: it relays a stop
-// and every workgroup exits), the others poll its relay; each reads the command words into LDS, and the workgroup runs the role-split rollout with
+// is rollout block b of every step.  Per step: the head's wave 0 polls the command's tagged slots (mppi_cmd.h: a
+// slot per lane, system scope) until every tag is the same sequence number >= `expect` (or the stop
+// slot names this launch, or idle_ticks pass without a command: it relays a stop and every workgroup
+// exits), the others poll its relay of the same slots; the poll's own load leaves the command words
+// in LDS, and the workgroup runs the role-split rollout with
 // the command's state, normals slot and nominal buffer.  Its record is written through and counted
 // (rec_cnt); the workgroups holding the last fin_groups tickets run the column-split finish, each
-// after rec_cnt reaches nroll (bounded by wait_ticks: a finish without every record publishes
+// after rec_cnt reaches nroll (the last ticket is that proof already; bounded by wait_ticks: a finish without every record publishes
 // done = seq | kDoneFail); the others generate the normals of step + 2 meanwhile (noise phase:
 // the chip is otherwise idle while the finish reduces and the host turns the step around).  No assumption on dispatch order or co-residency: a workgroup waits only
 // for records of workgroups that run or get a slot as others reach their wait.
@@ -3454,68 +3456,61 @@ __global__ __launch_bounds__(NROLES * TB) void mppi_step_server_kernel(const Ser
     const auto* L = fresh_args();
     const ServerArgs& z = L->z;
     if (tid < 64) {
-      // the head polls the pinned command (seq and stop in one 8-byte read) and relays it: the
-      // command words to relay[16..], then (after they completed) seq / stop to relay[0..1]; the
-      // others poll relay[0..1] in device memory.  An idle head relays a stop.  Stop words are this
-      // launch's launch_id (a stale one from an earlier launch never matches), so the host launches
-      // without resetting the relay or the command's stop word.
-      const unsigned long long* src = head ? reinterpret_cast<const unsigned long long*>(z.cmd)
-                                           : reinterpret_cast<const unsigned long long*>(z.relay);
+      // the head polls the pinned command and relays it; the others poll its relay in device memory.
+      // Both are the tagged slots of mppi_cmd.h, a slot per lane: one wave load per poll reads the
+      // stop word and every command word with its tag, and a sweep is the command once all tags
+      // agree (>= expect), so there is no second read behind the poll hit.  The head passes the very
+      // pairs on with one store instruction (agent scope, no drain, no separate seq word: the tags
+      // are the signal, as in the finish's u_opt handoff).  An idle head relays a stop.  Stop words
+      // are this launch's launch_id (a stale one from an earlier launch never matches), so the host
+      // launches without resetting the relay or the command's stop word.
+      const int slot = tid < kCmdWords ? tid : 0;
+      const unsigned long long* src =
+          (head ? reinterpret_cast<const unsigned long long*>(z.cmd->slot) : z.relay) + slot;
+      const unsigned* host_stop = reinterpret_cast<const unsigned*>(z.cmd->slot + kCmdStopSlot);
       // Only the head leaves on its own (idle limit, or the exit_after test hook); the others leave
       // on the stop it relays.  So an exit is all-or-nothing: either every workgroup serves a command
       // or none does, and a command the head never relayed leaves no trace of the step (the host sees
       // the launch retire without a completion word and relaunches the server with that command).
-      // The host's stop is read before seq (a stop posted before a later launch's command ends this
-      // launch first), and the others also read it themselves every ~100 us: after a finish that gave
-      // up no workgroup holds the last ticket, so there is no head to relay it.
+      // The stop is examined before the tags (a stop posted before a later launch's command ends this
+      // launch first), and the others also read the host's themselves every ~100 us: after a finish
+      // that gave up no workgroup holds the last ticket, so there is no head to relay it.
       unsigned ok = 0;
-      if (tid == 0) {
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        uint64_t t_stop = t0;
-        if (head && z.clk) z.clk[kClkServer + 8 * (expect & 7) + 6] = t0;
-        const bool forced = head && z.exit_after != 0 && expect - z.first_seq >= z.exit_after;
-        while (!forced) {
-          const unsigned long long w = head ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-                                            : __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((unsigned)(w >> 32) == z.launch_id) break;
-          if ((int)((unsigned)w - expect) >= 0) {
-            ok = 1;
-            break;
-          }
-          const uint64_t now = __builtin_amdgcn_s_memrealtime();
-          if (head) {
-            if (now - t0 >= z.idle_ticks) break;
-          } else {
-            if (now - t_stop >= 10000) {
-              t_stop = now;
-              if (__hip_atomic_load(&z.cmd->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == z.launch_id) break;
-            }
-            __builtin_amdgcn_s_sleep(2);  // (~0.06 us; 8: server rollout +0.4 us, its start spread)
-          }
+      unsigned long long w = 0;
+      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+      uint64_t t_stop = t0;
+      if (tid == 0 && head && z.clk) z.clk[kClkServer + 8 * (expect & 7) + 6] = t0;
+      const bool forced = head && z.exit_after != 0 && expect - z.first_seq >= z.exit_after;
+      while (!forced) {  // (wave-uniform: every exit is on a broadcast value or the scalar clock)
+        w = head ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
+                 : __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned lo = (unsigned)w, hi = (unsigned)(w >> 32);
+        const unsigned long long stop_slot = (unsigned)__builtin_amdgcn_readlane((int)lo, kCmdStopSlot);
+        if (cmd_stop_hit(stop_slot, z.launch_id)) break;
+        const unsigned seq0 = (unsigned)__builtin_amdgcn_readfirstlane((int)hi);
+        if (__builtin_amdgcn_ballot_w64(!cmd_slot_ok(slot, w, seq0, expect)) == 0) {
+          ok = 1;
+          break;
         }
-      }
-      ok = __builtin_amdgcn_readfirstlane(ok);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (compiler only: the words below after the poll)
-      if (ok && tid < kCmdWords) {
-        unsigned wv;
+        const uint64_t now = __builtin_amdgcn_s_memrealtime();
         if (head) {
-          wv = __hip_atomic_load(reinterpret_cast<const unsigned*>(z.cmd) + tid, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_SYSTEM);
-          __hip_atomic_store(z.relay + 16 + tid, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (now - t0 >= z.idle_ticks) break;
         } else {
-          wv = __hip_atomic_load(z.relay + 16 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        cmd_lds[tid] = wv;
-      }
-      if (head) {  // the words are written through and complete, then seq (or stop: every workgroup exits)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) {
-          if (ok)
-            __hip_atomic_store(z.relay, cmd_lds[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else
-            __hip_atomic_store(z.relay + 1, z.launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (now - t_stop >= 10000) {
+            t_stop = now;
+            if (__hip_atomic_load(host_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == z.launch_id) break;
+          }
+          __builtin_amdgcn_s_sleep(2);  // (~0.06 us; 8: server rollout +0.4 us, its start spread)
         }
       }
+      if (ok && tid < kCmdWords) {
+        if (head && tid != kCmdStopSlot)
+          __hip_atomic_store(z.relay + tid, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cmd_lds[tid] = (unsigned)w;
+      }
+      if (head && !ok && tid == 0)  // (stop, idle or the exit hook: every workgroup exits)
+        __hip_atomic_store(z.relay + kCmdStopSlot, (unsigned long long)z.launch_id, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
       if (tid == 0) cmd_lds[31] = ok;
       if (tid == 0 && head && z.clk && ok)  // (write-through: the last ticket and the finish read it)
         __hip_atomic_store(z.clk + kClkServer + 8 * (cmd_lds[0] & 7), (uint64_t)__builtin_amdgcn_s_memrealtime(),
@@ -3582,7 +3577,10 @@ __global__ __launch_bounds__(NROLES * TB) void mppi_step_server_kernel(const Ser
       if (tid == 0) {  // bounded (z.wait_ticks of the 100 MHz clock): a lost count cannot hang the device
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         int late = z.wait_ticks == 0;  // 0: give up at once (the test hook of mppi_set_option)
-        while (!late && __hip_atomic_load(z.rec_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)z.nroll) {
+        // (the last ticket needs no poll: every other record was drained before its own count, and
+        // this workgroup's add, which returned nroll - 1, came after all of them)
+        while (!late && ticket != z.nroll - 1 &&
+               __hip_atomic_load(z.rec_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)z.nroll) {
           // (another finish workgroup gave up on this step: the step has failed, stop waiting)
           if (__builtin_amdgcn_s_memrealtime() - t0 >= z.wait_ticks ||
               __hip_atomic_load(z.f.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == seq) {
@@ -3710,3 +3708,4 @@ hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, floa
 }
 
 }  // namespace mppi
+

@@ -1,0 +1,205 @@
+// Batched closed-loop episodes (mppi_batch_*).  Included by mppi_kernels.hip inside
+// namespace mppi: the kernels are built from its device functions (noise_waves, roles_body,
+// pair_scale / group_apply, finish_phase2) and compute the bits of the single-context step.
+//
+// Three plain stream-ordered launches per step, each with a grid dimension for the episode; an
+// episode's state lives in its BatchEpisode record (device memory), read with wave-uniform loads
+// where a single-context step reads kernel arguments.  No workgroup waits for another or for the
+// host (apart from roles_body's own in-workgroup LDS rings).
+#pragma once
+
+// The normals of every active episode's current step, [blocks][2][H][256] per episode, addressed as
+// mppi_noise_kernel addresses them: key = the episode's seed, Philox block step * ((H + 1) / 2) +
+// t / 2, global trajectory index.  Grid (G, E), four waves per workgroup; wave w of workgroup g takes
+// the wave-units 4 g + w, + 4 G, ... of the episode (noise_waves).
+__global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b, int64_t k_offset) {
+  const int e = blockIdx.y;
+  const BatchEpisode* ep = b.ep + e;
+  if (!ep->active) return;
+  const int H = b.H, NB = (H + 1) >> 1;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  float* eps = b.eps + (size_t)e * b.blocks * 2 * H * 256;
+  noise_waves(ep->seed, ep->step * (uint64_t)NB, k_offset, H, (int)blockIdx.x * 4 + wave, b.blocks * NB * 4,
+              (int)gridDim.x * 4, eps, (int)threadIdx.x & 63);
+}
+
+// The role-split rollout of leaf block blockIdx.x of episode blockIdx.y: the launch's RolloutArgs
+// (scene and parameters) with the episode's state, derived critic fields, seed, Philox base and
+// buffer slices patched in.
+template <int PROJ>
+__global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const RolloutArgs a_in, const BatchArgs b) {
+  const int e = blockIdx.y;
+  const BatchEpisode* ep = b.ep + e;
+  if (!ep->active) return;
+  RolloutArgs a = a_in;
+  const int H = a.H;
+  a.x0 = ep->x0;
+  a.y0 = ep->y0;
+  a.h0x = ep->h0x;
+  a.h0y = ep->h0y;
+  a.h0z = ep->h0z;
+  a.wl = ep->wl;
+  a.wr = ep->wr;
+  a.gx = ep->gx;
+  a.gy = ep->gy;
+  a.s1 = ep->s1;
+  a.s2 = ep->s2;
+  a.pf_far = ep->pf_far;
+  a.speed_on = ep->speed_on;
+  a.igx = ep->igx;
+  a.igy = ep->igy;
+  a.pf_scale = ep->pf_scale;
+  a.seed = ep->seed;
+  a.n_base = ep->step * (uint64_t)((H + 1) >> 1);
+  a.eps = b.eps + (size_t)e * b.blocks * 2 * H * 256;
+  const float* unom = b.unom + ((size_t)e * 2 + ep->cur) * 2 * H;
+  a.u_nom1 = unom;
+  a.u_nom2 = unom + H;
+  a.cost_out = b.cost + (size_t)e * b.k_pad;
+  a.nodes = b.nodes + (size_t)e * b.blocks * (2 * H + 2);
+  roles_body<256, PROJ, 0, false, false>(a, (int)blockIdx.x, nullptr);
+}
+
+// One workgroup per episode: the binary tree over its leaf records (tree_reduce of the oracle: the
+// count padded to a power of two with empty records; one aligned group of 16 with the empty members
+// passing their partners through, as the last pass of mppi_finish_kernel), the mode-2 phase 2 (u_opt
+// into the other half of the nominal double buffer, the filtered v / w, row 0 of the optimal
+// rollout), then one lane advances the episode by the closed loop's rule (MPPI_Controller.run,
+// MPPI_isaac.py:769-784; mppi_amd/batch.py advance_state is the same arithmetic on the host).
+__global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int e = blockIdx.x;
+  BatchEpisode* ep = b.ep + e;
+  if (!ep->active) return;
+  const int tid = threadIdx.x;
+  FinishArgs f = f_in;
+  const int H = f.H, E = 2 * H + 2;
+  const int cur_buf = ep->cur;
+  const float gx = ep->gx, gy = ep->gy;
+  const int row = ep->steps_run;
+  f.mode = 2;
+  f.done = nullptr;
+  f.x0 = ep->x0;
+  f.y0 = ep->y0;
+  f.h0x = ep->h0x;
+  f.h0y = ep->h0y;
+  f.h0z = ep->h0z;
+  f.wl = ep->wl;
+  f.wr = ep->wr;
+  f.u_nom_next = b.unom + ((size_t)e * 2 + (cur_buf ^ 1)) * 2 * H;
+  f.out = b.fin + (size_t)e * (7 * H + 12);
+  f.tail_in = f.out + 4 * H + 12;
+  // ---------------- (1) tree: the n <= 16 records -> root in lnode[0..E)
+  double* lnode = reinterpret_cast<double*>(smem_raw);
+  PairScale* lps = reinterpret_cast<PairScale*>(smem_raw + (size_t)E * sizeof(double));
+  const double* recs = b.nodes + (size_t)e * b.blocks * E;
+  const int n = b.blocks;
+  if (n > 1) {
+    float* lm = reinterpret_cast<float*>(lps + 15);
+    if (tid < 16) lm[tid] = (tid < n) ? (float)recs[(size_t)tid * E] : INFINITY;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1) {
+      PairScale p;
+      if (tid < w) {
+        p = pair_scale(lm[2 * tid], lm[2 * tid + 1], f.T);
+        lps[base + tid] = p;
+      }
+      __syncthreads();
+      if (tid < w) lm[tid] = p.m;
+      __syncthreads();
+      base += w;
+    }
+    for (int j = tid; j < E; j += FIN_THREADS) {
+      double v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = recs[(size_t)min(i, n - 1) * E + j];
+      lnode[j] = group_apply<16>(lps, v, j);
+    }
+  } else {
+    for (int j = tid; j < E; j += FIN_THREADS) lnode[j] = recs[j];
+  }
+  __syncthreads();
+  // ---------------- (2) u_opt = V / S (zero when no trajectory has a finite cost) and phase 2
+  const double S = lnode[1];
+  const float ures = (tid < 2 * H && S > 0.0) ? (float)(lnode[2 + tid] / S) : 0.0f;
+  __syncthreads();  // lnode is dead from here on
+  finish_phase2(f, ures, smem_raw, tid, FIN_THREADS);
+  // ---------------- (3) advance (finish_phase2 ends with every output store complete and a barrier;
+  // the outputs were written through, so agent-scope loads see them)
+  if (tid != 0) return;
+  auto ld = [&](int i) __attribute__((always_inline)) {
+    return __hip_atomic_load(f.out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const float v = ld(2 * H), w = ld(3 * H);
+  const float x = ld(4 * H), y = ld(4 * H + 1), z = ld(4 * H + 2);
+  // heading: row 0 widened to float64 and divided by its norm ((a a + b b) + c c, no fma), each
+  // component rounded to float32 (robot.heading_vector / np.linalg.norm, MPPI_isaac.py:493)
+  const double d0 = (double)ld(4 * H + 3), d1 = (double)ld(4 * H + 4), d2 = (double)ld(4 * H + 5);
+  const double nn = __builtin_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+  const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
+  if (row < b.log_cap) {
+    float* lg = b.log + ((size_t)e * b.log_cap + row) * 8;
+    lg[0] = x;
+    lg[1] = y;
+    lg[2] = z;
+    lg[3] = hx;
+    lg[4] = hy;
+    lg[5] = hz;
+    lg[6] = v;
+    lg[7] = w;
+  }
+  const float ww = (w * w) / b.sigma_div;
+  const float half = (w * b.rwheel) / 2.0f;
+  ep->x0 = x;
+  ep->y0 = y;
+  ep->h0x = hx;
+  ep->h0y = hy;
+  ep->h0z = hz;
+  ep->wl = v - half;
+  ep->wr = v + half;
+  ep->s1 = fmaxf(b.sigma_base, b.sigma_base - ww);
+  ep->s2 = fmaxf(b.sigma_base, b.sigma_base + ww);
+  {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
+    const float xd = gx - x;
+    const float yd = gy - y;
+    const float dist = sqrtf(xd * xd + yd * yd);
+    const float horizon = b.horizon;
+    ep->pf_far = dist > horizon ? 1 : 0;
+    ep->igx = x + (xd * horizon) / (dist + 1e-6f);
+    ep->igy = y + (yd * horizon) / (dist + 1e-6f);
+    ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
+    ep->speed_on = (dist < 2.0f) ? 0 : 1;
+  }
+  ep->cur = cur_buf ^ 1;
+  ep->step = ep->step + 1;
+  ep->steps_run = row + 1;
+  if (!(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol)) {
+    ep->active = 0;
+    ep->reached = 1;
+    __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
+  // about four wave-units (two noise_waves iterations) per wave
+  const int units = b.blocks * ((b.H + 1) >> 1) * 4;
+  const unsigned g = (unsigned)std::min(std::max((units + 15) / 16, 1), 64);
+  hipLaunchKernelGGL(mppi_batch_noise_kernel, dim3(g, (unsigned)b.E), dim3(256), 0, st, b, k_offset);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj) {
+  const dim3 g((unsigned)b.blocks, (unsigned)b.E), t(NROLES * 256);
+  if (proj == 3)
+    hipLaunchKernelGGL(mppi_batch_rollout_kernel<3>, g, t, lds, st, a, b);
+  else
+    hipLaunchKernelGGL(mppi_batch_rollout_kernel<2>, g, t, lds, st, a, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b);
+  return hipGetLastError();
+}

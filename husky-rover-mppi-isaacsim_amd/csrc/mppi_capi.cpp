@@ -2809,3 +2809,296 @@ int mppi_group_step(mppi_group* g, int32_t proj, uint64_t step, mppi_outputs* ou
 }
 
 }  // extern "C"
+
+// ---- batched closed-loop episodes (mppi_batch_*) ----
+
+struct mppi_batch {
+  mppi_ctx* c = nullptr;
+  int E = 0, blocks = 0, H = 0;
+  std::vector<BatchEpisode> host;     // the table as last read from / written to the device
+  std::vector<unsigned char> is_set;  // mppi_batch_set_episode was called for the episode
+  BatchEpisode* ep = nullptr;
+  float* eps = nullptr;
+  float* unom = nullptr;
+  double* nodes = nullptr;
+  float* cost = nullptr;
+  float* fin = nullptr;
+  float* log = nullptr;
+  size_t log_bytes = 0;
+  int log_cap = 0;
+  int* active_count = nullptr;  // pinned
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double last_ms = 0;
+  bool failed = false;  // a HIP error of the batch: further runs are refused
+};
+
+namespace {
+
+int batch_episode(mppi_batch* b, int32_t e) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (e < 0 || e >= b->E) return fail(MPPI_EINVAL, "episode index out of range");
+  return MPPI_OK;
+}
+
+// The episode table device -> host (waits for the context stream).
+int batch_pull(mppi_batch* b) {
+  mppi_ctx* c = b->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(b->host.data(), b->ep, (size_t)b->E * sizeof(BatchEpisode), hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol) {
+  mppi_ctx* c = b->c;
+  const Plan pl = make_plan(c);
+  if (!pl.roles || pl.blocks != b->blocks)
+    return fail(MPPI_ESTATE, "batch: the context does not run the role-split rollout plan (MPPI_ROLES=0)");
+  int rc = batch_pull(b);
+  if (rc) return rc;
+  int active = 0;
+  for (int e = 0; e < b->E; ++e) {
+    BatchEpisode& r = b->host[e];
+    r.steps_run = 0;
+    const bool outside = std::fabs(r.x0 - r.gx) > pol.goal_tol || std::fabs(r.y0 - r.gy) > pol.goal_tol;
+    r.active = b->is_set[e] && outside ? 1 : 0;
+    if (b->is_set[e] && !outside) r.reached = 1;
+    active += r.active;
+  }
+  b->last_ms = 0;
+  if (n_steps == 0 || active == 0) {
+    HIP_TRY(hipMemcpyAsync(b->ep, b->host.data(), (size_t)b->E * sizeof(BatchEpisode), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPPI_OK;
+  }
+  const size_t log_need = (size_t)b->E * n_steps * 8 * sizeof(float);
+  rc = grow(b->log, b->log_bytes, log_need, c->stream);
+  if (rc) return rc;
+  b->log_cap = n_steps;
+  HIP_TRY(hipMemcpyAsync(b->ep, b->host.data(), (size_t)b->E * sizeof(BatchEpisode), hipMemcpyHostToDevice,
+                         c->stream));
+  __atomic_store_n(b->active_count, active, __ATOMIC_RELEASE);
+
+  RolloutArgs a;
+  FinishArgs f;
+  const mppi_state none{};
+  fill_rollout(c, pl, none, 0, nullptr, a);  // scene and parameters; the kernel patches the episode's part
+  a.clk = nullptr;
+  a.rec_m = nullptr;
+  a.ustore = nullptr;
+  a.inj_u1 = a.inj_u2 = nullptr;
+  a.k_offset = c->p.k_offset;
+  fill_finish(c, pl, none, f);
+  f.mode = 2;
+  BatchArgs z{};
+  z.ep = b->ep;
+  z.E = b->E;
+  z.blocks = b->blocks;
+  z.H = b->H;
+  z.k_pad = (int64_t)b->blocks * 256;
+  z.eps = b->eps;
+  z.unom = b->unom;
+  z.nodes = b->nodes;
+  z.cost = b->cost;
+  z.fin = b->fin;
+  z.log = b->log;
+  z.log_cap = b->log_cap;
+  z.sigma_base = pol.sigma_base;
+  z.sigma_div = pol.sigma_div;
+  z.goal_tol = pol.goal_tol;
+  z.horizon = c->p.horizon;
+  z.rwheel = c->p.robot_radius;
+  z.active_count = b->active_count;
+  const int every = pol.check_every > 0 ? pol.check_every : 16;
+  HIP_TRY(hipEventRecord(b->ev[0], c->stream));
+  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count, __ATOMIC_ACQUIRE) > 0;) {
+    const int m = std::min(every, n_steps - done);
+    for (int i = 0; i < m; ++i) {
+      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+      HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, proj));
+      HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    done += m;
+  }
+  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
+  HIP_TRY(hipEventSynchronize(b->ev[1]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+  b->last_ms = ms;
+  return MPPI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mppi_batch_create(mppi_ctx* c, int32_t episodes, mppi_batch** out) {
+  if (!out) return fail(MPPI_EINVAL, "null argument");
+  *out = nullptr;
+  if (episodes < 1 || episodes > 4096) return fail(MPPI_EINVAL, "episodes must be in [1, 4096]");
+  if (!c) return fail(MPPI_EINVAL, "null context");
+  const int64_t K = c->p.num_trajectories;
+  const int64_t blocks = (K + PAIR_TRAJ - 1) / PAIR_TRAJ;
+  if (blocks < 1 || blocks > kBatchMaxRecords)
+    return fail(MPPI_EINVAL, "batch: num_trajectories must be in [1, 4096] (1 to 16 leaf records)");
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  mppi_batch* b = new mppi_batch();
+  b->c = c;
+  b->E = episodes;
+  b->blocks = (int)blocks;
+  const int H = b->H = H_of(c);
+  const size_t E = (size_t)episodes;
+  b->host.assign(E, BatchEpisode{});
+  b->is_set.assign(E, 0);
+  if (hipMalloc(&b->ep, E * sizeof(BatchEpisode)) != hipSuccess ||
+      hipMalloc(&b->eps, E * blocks * 2 * H * 256 * sizeof(float)) != hipSuccess ||
+      hipMalloc(&b->unom, E * 4 * H * sizeof(float)) != hipSuccess ||
+      hipMalloc(&b->nodes, E * blocks * (2 * H + 2) * sizeof(double)) != hipSuccess ||
+      hipMalloc(&b->cost, E * blocks * 256 * sizeof(float)) != hipSuccess ||
+      hipMalloc(&b->fin, E * (7 * H + 12) * sizeof(float)) != hipSuccess ||
+      hipHostMalloc(&b->active_count, 64, hipHostMallocDefault) != hipSuccess ||
+      hipEventCreate(&b->ev[0]) != hipSuccess || hipEventCreate(&b->ev[1]) != hipSuccess ||
+      hipMemset(b->ep, 0, E * sizeof(BatchEpisode)) != hipSuccess ||
+      hipMemset(b->unom, 0, E * 4 * H * sizeof(float)) != hipSuccess ||
+      hipMemset(b->cost, 0, E * blocks * 256 * sizeof(float)) != hipSuccess ||
+      hipMemset(b->fin, 0, E * (7 * H + 12) * sizeof(float)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {
+    const std::string why = hipGetErrorString(hipGetLastError());
+    mppi_batch_destroy(b);
+    return fail(MPPI_EHIP, "batch allocation failed: " + why);
+  }
+  *b->active_count = 0;
+  *out = b;
+  return MPPI_OK;
+}
+
+void mppi_batch_destroy(mppi_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->c->device);
+  if (b->c->stream) hipStreamSynchronize(b->c->stream);
+  if (b->ep) hipFree(b->ep);
+  if (b->eps) hipFree(b->eps);
+  if (b->unom) hipFree(b->unom);
+  if (b->nodes) hipFree(b->nodes);
+  if (b->cost) hipFree(b->cost);
+  if (b->fin) hipFree(b->fin);
+  if (b->log) hipFree(b->log);
+  if (b->active_count) hipHostFree(b->active_count);
+  for (hipEvent_t e : b->ev)
+    if (e) hipEventDestroy(e);
+  delete b;
+}
+
+int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, uint64_t seed) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (!start) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  ServerCmd d;
+  state_fields(c->p, *start, d);
+  BatchEpisode r{};
+  r.x0 = d.x0;
+  r.y0 = d.y0;
+  r.h0x = d.h0x;
+  r.h0y = d.h0y;
+  r.h0z = d.h0z;
+  r.wl = d.wl;
+  r.wr = d.wr;
+  r.gx = d.gx;
+  r.gy = d.gy;
+  r.s1 = d.s1;
+  r.s2 = d.s2;
+  r.pf_far = d.pf_far;
+  r.speed_on = d.speed_on;
+  r.igx = d.igx;
+  r.igy = d.igy;
+  r.pf_scale = d.pf_scale;
+  r.seed = seed;
+  b->host[e] = r;
+  b->is_set[e] = 1;
+  HIP_TRY(hipMemcpyAsync(b->ep + e, &b->host[e], sizeof(BatchEpisode), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->unom + (size_t)e * 4 * b->H, 0, (size_t)4 * b->H * sizeof(float), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop_policy* policy) {
+  if (!b || !policy) return fail(MPPI_EINVAL, "null argument");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  if (n_steps < 0) return fail(MPPI_EINVAL, "n_steps must be >= 0");
+  if (policy->check_every < 0) return fail(MPPI_EINVAL, "check_every must be >= 0");
+  if (!(policy->sigma_div != 0.0f)) return fail(MPPI_EINVAL, "sigma_div must be non-zero");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (!c->Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
+  if (!c->cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = batch_run(b, proj, n_steps, *policy);
+  if (rc == MPPI_EHIP) b->failed = true;
+  return rc;
+}
+
+int mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total,
+                           int32_t* steps_last_run, int32_t* reached, float* u1, float* u2) {
+  if (int rc = batch_episode(b, e)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  BatchEpisode& r = b->host[e];
+  const int H = b->H;
+  HIP_TRY(hipMemcpyAsync(&r, b->ep + e, sizeof(BatchEpisode), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const float* unom = b->unom + ((size_t)e * 2 + r.cur) * 2 * H;
+  if (u1) HIP_TRY(hipMemcpyAsync(u1, unom, H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (u2) HIP_TRY(hipMemcpyAsync(u2, unom + H, H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (u1 || u2) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (state) {
+    state->x = r.x0;
+    state->y = r.y0;
+    state->heading[0] = r.h0x;
+    state->heading[1] = r.h0y;
+    state->heading[2] = r.h0z;
+    state->left_wheel_speed = r.wl;
+    state->right_wheel_speed = r.wr;
+    state->goal_x = r.gx;
+    state->goal_y = r.gy;
+    state->std_dev_u1 = r.s1;
+    state->std_dev_u2 = r.s2;
+  }
+  if (steps_total) *steps_total = (int64_t)r.step;
+  if (steps_last_run) *steps_last_run = r.steps_run;
+  if (reached) *reached = r.reached;
+  return MPPI_OK;
+}
+
+int mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "log range out of bounds");
+  if (count > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  BatchEpisode& r = b->host[e];
+  HIP_TRY(hipMemcpyAsync(&r, b->ep + e, sizeof(BatchEpisode), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((int64_t)first + count > r.steps_run) return fail(MPPI_EINVAL, "log range beyond the steps of the last run");
+  if (count == 0) return MPPI_OK;
+  HIP_TRY(hipMemcpyAsync(rows, b->log + ((size_t)e * b->log_cap + first) * 8, (size_t)count * 8 * sizeof(float),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_get_ms(mppi_batch* b, double* ms) {
+  if (!b || !ms) return fail(MPPI_EINVAL, "null argument");
+  *ms = b->last_ms;
+  return MPPI_OK;
+}
+
+}  // extern "C"

@@ -192,6 +192,44 @@ hipError_t launch_cdiv_verify(float b, float y, unsigned* bad, hipStream_t st);
 // laid out [blocks][2][H][256]: eps1 rows then eps2 rows, 256 trajectories per row.
 hipError_t launch_noise(uint64_t seed, uint64_t n_base, int64_t k_offset, int blocks, int H, float* eps,
                         hipStream_t st, int max_groups);
+// ---- batched closed-loop episodes (mppi_batch_*) ----
+// E independent episodes over one context's scene and parameters, advanced by three stream-ordered
+// launches per step (normals, rollout, finish-and-advance) with the loop's state feedback on the GPU.
+// One record per episode in device memory: what a single-context step takes from mppi_state and
+// state_fields() (mppi_capi.cpp) as kernel arguments, plus the loop's own counters.
+struct BatchEpisode {
+  float x0, y0, h0x, h0y, h0z, wl, wr, gx, gy, s1, s2;  // mppi_state
+  int pf_far, speed_on;                                 // state_fields(): the critics' scalar parts
+  float igx, igy, pf_scale;
+  int active;      // runs the next step (runnable and outside the goal tolerance)
+  int cur;         // the half of the nominal double buffer the next step reads
+  uint64_t seed;   // Philox key
+  uint64_t step;   // Philox step index (steps since mppi_batch_set_episode)
+  int steps_run;   // steps of the current run = rows in the episode's log
+  int reached;     // the goal test passed
+};
+static_assert(sizeof(BatchEpisode) == 96, "BatchEpisode layout");
+struct BatchArgs {
+  BatchEpisode* ep;  // [E]
+  int E, blocks, H;
+  int64_t k_pad;     // blocks * 256
+  float* eps;        // [E][blocks][2][H][256] this step's normals
+  float* unom;       // [E][2][2H] nominal double buffer
+  double* nodes;     // [E][blocks][2H + 2] leaf records
+  float* cost;       // [E][k_pad]
+  float* fin;        // [E][7H + 12]: the mode-2 finish outputs (u1, u2, v, w [H], row 0 [12]), then its
+                     // tail inputs [3H] (written by finish_phase2, not read: the loop consumes row 0 only)
+  float* log;        // [E][log_cap][8]: x, y, z, heading, v, w per step of the run
+  int log_cap;
+  float sigma_base, sigma_div, goal_tol;  // mppi_loop_policy
+  float horizon, rwheel;                  // mppi_params horizon, robot_radius
+  int* active_count;                      // pinned host memory: episodes still active
+};
+constexpr int kBatchMaxRecords = 16;  // leaf records per episode: the finish's tree is one LDS pass
+hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st);
+hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);
+hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st);
+
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);
 // LDS-tiled lookup over queries binned by BIL_TILE x BIL_TILE-cell DEM tile (tile count =

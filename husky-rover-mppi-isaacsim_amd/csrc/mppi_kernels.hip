@@ -3707,5 +3707,8 @@ hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, floa
   return hipGetLastError();
 }
 
+// =====================================================================  batched closed-loop episodes
+#include "mppi_batch_kernels.h"
+
 }  // namespace mppi
 

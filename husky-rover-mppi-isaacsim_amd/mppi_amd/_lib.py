@@ -67,6 +67,12 @@ class MppiPathScores(C.Structure):
     _fields_ = [("cost", _FP), ("terms", _FP), ("collisions", C.POINTER(C.c_int32))]
 
 
+class MppiLoopPolicy(C.Structure):
+    """mppi_loop_policy: the closed loop's sigma schedule and goal test (mppi_batch_run)."""
+    _fields_ = [("sigma_base", C.c_float), ("sigma_div", C.c_float), ("goal_tol", C.c_float),
+                ("check_every", C.c_int32)]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
 
 
@@ -131,6 +137,14 @@ _PROTOS = {
     "mppi_group_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(MppiOutputs)]),
     "mppi_group_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]),
     "mppi_group_selftest": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "mppi_batch_create": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mppi_batch_destroy": (None, [C.c_void_p]),
+    "mppi_batch_set_episode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiState), C.c_uint64]),
+    "mppi_batch_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MppiLoopPolicy)]),
+    "mppi_batch_get_episode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiState), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, _FP]),
+    "mppi_batch_get_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_get_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
                                          C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_int32)]),
 }
@@ -603,6 +617,74 @@ class Engine:
     def bilinear_query(self, x_ptr, y_ptr, h_ptr, n):
         self._c(self.lib.mppi_bilinear_query(self.ctx, C.c_void_p(int(x_ptr)), C.c_void_p(int(y_ptr)),
                                              C.c_void_p(int(h_ptr)), int(n)), "mppi_bilinear_query")
+
+
+def make_policy(sigma_base=0.4, sigma_div=1.0, goal_tol=0.5, check_every=0):
+    """Fill mppi_loop_policy (defaults: run()'s policy; check_every 0 = the library's 16)."""
+    return MppiLoopPolicy(float(sigma_base), float(sigma_div), float(goal_tol), int(check_every))
+
+
+class Batch:
+    """mppi_batch (include/mppi.h): E closed-loop episodes over one Engine's scene and parameters,
+    advanced on the GPU with no host work between steps.  Keeps a reference to its Engine, so the
+    context cannot be freed first."""
+
+    def __init__(self, engine: "Engine", episodes: int):
+        self.engine = engine
+        self.lib = engine.lib
+        self.E = int(episodes)
+        self.H = engine.H
+        h = C.c_void_p()
+        _check(self.lib, self.lib.mppi_batch_create(engine.ctx, self.E, C.byref(h)), "mppi_batch_create")
+        self.h = h
+
+    def set_episode(self, e, state: MppiState, seed):
+        _check(self.lib, self.lib.mppi_batch_set_episode(self.h, int(e), C.byref(state),
+                                                         int(seed) & 0xFFFFFFFFFFFFFFFF),
+               "mppi_batch_set_episode")
+
+    def run(self, n_steps, proj="3d", policy=None):
+        """Advance every active episode by up to n_steps steps (policy: MppiLoopPolicy, default run()'s)."""
+        pol = policy if policy is not None else make_policy()
+        _check(self.lib, self.lib.mppi_batch_run(self.h, PROJ[proj], int(n_steps), C.byref(pol)), "mppi_batch_run")
+
+    def episode(self, e):
+        """dict(state (MppiState), steps_total, steps_last_run, reached, u1, u2 (the next nominal sequence))."""
+        st = MppiState()
+        total, last, reached = C.c_int64(), C.c_int32(), C.c_int32()
+        u1 = np.zeros(self.H, np.float32)
+        u2 = np.zeros(self.H, np.float32)
+        _check(self.lib, self.lib.mppi_batch_get_episode(self.h, int(e), C.byref(st), C.byref(total), C.byref(last),
+                                                         C.byref(reached), _fp(u1), _fp(u2)),
+               "mppi_batch_get_episode")
+        return dict(state=st, steps_total=total.value, steps_last_run=last.value, reached=bool(reached.value),
+                    u1=u1, u2=u2)
+
+    def log(self, e, first=0, count=None):
+        """Rows [count, 8] of the most recent run: x, y, z, the normalised heading, v, w per step."""
+        if count is None:
+            count = self.episode(e)["steps_last_run"] - int(first)
+        rows = np.zeros((max(int(count), 0), 8), np.float32)
+        _check(self.lib, self.lib.mppi_batch_get_log(self.h, int(e), int(first), int(count), _fp(rows)),
+               "mppi_batch_get_log")
+        return rows
+
+    def last_ms(self):
+        ms = C.c_double()
+        _check(self.lib, self.lib.mppi_batch_get_ms(self.h, C.byref(ms)), "mppi_batch_get_ms")
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            if self.engine.ctx and self.engine.ctx.value:   # (a closed engine took its stream along)
+                self.lib.mppi_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def debug_hold(device, stream_handle, groups, lds_bytes, microseconds):

@@ -1,0 +1,88 @@
+"""The closed loop's advance rule (MPPI_Controller.run, MPPI_isaac.py:769-784), explicit.
+
+This is the host's half of the contract of the batched episodes (include/mppi.h, mppi_batch_*;
+DESIGN.md §3.7): the finish-and-advance kernel applies the same arithmetic on the GPU after every
+step.  Plain numpy float32 / float64, usable without a GPU or the library.
+
+A state is a dict with the fields of mppi_state: x, y, heading (3 values), left_wheel_speed,
+right_wheel_speed, goal_x, goal_y, std_dev_u1, std_dev_u2.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+F32 = np.float32
+
+RUN_POLICY = dict(sigma_base=0.4, sigma_div=1.0, goal_tol=0.5)      # MPPI_isaac.py:763-784
+ISAAC_POLICY = dict(sigma_base=0.25, sigma_div=3.0, goal_tol=0.5)   # visual_terrain_stack_full_terrain.py:510-511
+
+STATE_FIELDS = ("x", "y", "heading", "left_wheel_speed", "right_wheel_speed", "goal_x", "goal_y",
+                "std_dev_u1", "std_dev_u2")
+
+
+def normalise_heading(hv):
+    """Row 0 of heading_sim widened to float64 and divided by sqrt((h0 h0 + h1 h1) + h2 h2) (the sum
+    left to right, every operation rounded once), each component rounded to float32."""
+    h = np.asarray(hv, dtype=F32).astype(np.float64)
+    n = np.sqrt((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2])
+    return np.array([h[0] / n, h[1] / n, h[2] / n], dtype=np.float64).astype(F32)
+
+
+def is_active(state, policy=None):
+    """The loop's condition before a step: |x - goal_x| > tol or |y - goal_y| > tol, in float32."""
+    tol = F32((policy or RUN_POLICY)["goal_tol"])
+    x, y = F32(state["x"]), F32(state["y"])
+    gx, gy = F32(state["goal_x"]), F32(state["goal_y"])
+    return bool(np.abs(x - gx) > tol or np.abs(y - gy) > tol)
+
+
+def advance_state(state, traj0, heading0, v, w, robot_radius, policy=None):
+    """The state after one closed-loop step.
+
+    traj0, heading0: row 0 of the optimal rollout (traj_sim[0], heading_sim[0]); v, w: element 0 of
+    the filtered optimal velocities; robot_radius: params.robot_radius; policy: dict(sigma_base,
+    sigma_div, goal_tol), default run()'s.  Returns (new state dict, log row [8] float32: x, y, z,
+    the normalised heading, v, w).  Every value is float32; the goal is unchanged.
+    """
+    pol = policy or RUN_POLICY
+    base, div = F32(pol["sigma_base"]), F32(pol["sigma_div"])
+    t = np.asarray(traj0, dtype=F32)
+    v, w, r = F32(v), F32(w), F32(robot_radius)
+    h = normalise_heading(heading0)
+    ww = F32(F32(w * w) / div)
+    half = F32(F32(w * r) / F32(2.0))
+    new = dict(
+        x=t[0], y=t[1], heading=h,
+        left_wheel_speed=F32(v - half), right_wheel_speed=F32(v + half),
+        goal_x=F32(state["goal_x"]), goal_y=F32(state["goal_y"]),
+        std_dev_u1=np.maximum(base, F32(base - ww)), std_dev_u2=np.maximum(base, F32(base + ww)))
+    row = np.array([t[0], t[1], t[2], h[0], h[1], h[2], v, w], dtype=F32)
+    return new, row
+
+
+def state_dict(x, y, heading=(1.0, 0.0, 0.0), left_wheel_speed=0.0, right_wheel_speed=0.0, goal_x=0.0,
+               goal_y=0.0, std_dev_u1=0.25, std_dev_u2=0.25):
+    """A state dict in float32, the heading used as given."""
+    return dict(x=F32(x), y=F32(y), heading=np.asarray(heading, dtype=F32).copy(),
+                left_wheel_speed=F32(left_wheel_speed), right_wheel_speed=F32(right_wheel_speed),
+                goal_x=F32(goal_x), goal_y=F32(goal_y), std_dev_u1=F32(std_dev_u1), std_dev_u2=F32(std_dev_u2))
+
+
+def to_mppi_state(state):
+    """The ctypes MppiState of a state dict (the heading as given, no renormalisation)."""
+    from . import _lib
+    s = _lib.MppiState()
+    s.x, s.y = float(state["x"]), float(state["y"])
+    for i in range(3):
+        s.heading[i] = float(state["heading"][i])
+    s.left_wheel_speed = float(state["left_wheel_speed"])
+    s.right_wheel_speed = float(state["right_wheel_speed"])
+    s.goal_x, s.goal_y = float(state["goal_x"]), float(state["goal_y"])
+    s.std_dev_u1, s.std_dev_u2 = float(state["std_dev_u1"]), float(state["std_dev_u2"])
+    return s
+
+
+def from_mppi_state(s):
+    """The state dict of a ctypes MppiState."""
+    return state_dict(s.x, s.y, [s.heading[0], s.heading[1], s.heading[2]], s.left_wheel_speed,
+                      s.right_wheel_speed, s.goal_x, s.goal_y, s.std_dev_u1, s.std_dev_u2)

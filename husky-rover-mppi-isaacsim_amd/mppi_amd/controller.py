@@ -476,6 +476,46 @@ class MPPI_Controller:
             self.loop += 1
         print("Number of loops:", self.loop)
 
+    def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None):
+        """run() for many episodes at once on this controller's surface and parameters (mppi_batch_*,
+        DESIGN.md §3.7): episode e starts at starts[e] = (x, y) with heading headings[e] (normalised
+        as Robot does), wheels at rest and the controller's std_dev_u1 / std_dev_u2, and drives to
+        goals[e] = (x, y); the loop's state feedback runs on the GPU, no host work between steps.
+
+        seeds: Philox key per episode (default the controller's seed + e); max_loops: the step cap
+        (default the controller's); policy: dict(sigma_base, sigma_div, goal_tol[, check_every])
+        (default run()'s).  The robot and the controller's own loop state are not touched.  Returns
+        one dict per episode: x, y, z, lin_vel, ang_vel (the lists Robot accumulates: x, y, z begin
+        with the start pose and z = 0), loops, reached.
+        """
+        starts = np.asarray(starts, np.float64).reshape(-1, 2)
+        E = starts.shape[0]
+        headings = np.asarray(headings, np.float64).reshape(E, 3)
+        goals = np.asarray(goals, np.float64).reshape(E, 2)
+        seeds = [self.seed + e for e in range(E)] if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != E:
+            raise ValueError(f"{E} episodes but {len(seeds)} seeds")
+        if self.engine is None:
+            self.warp_setup()
+        pol = _lib.make_policy(**(policy or {}))
+        batch = _lib.Batch(self.engine, E)
+        try:
+            for e in range(E):
+                batch.set_episode(e, _lib.make_state(starts[e, 0], starts[e, 1], headings[e], 0.0, 0.0,
+                                                     goals[e, 0], goals[e, 1], self.std_dev_u1, self.std_dev_u2),
+                                  seeds[e])
+            batch.run(self.max_loops if max_loops is None else int(max_loops), proj, pol)
+            out = []
+            for e in range(E):
+                info = batch.episode(e)
+                rows = batch.log(e, 0, info["steps_last_run"])
+                out.append(dict(x=[starts[e, 0]] + list(rows[:, 0]), y=[starts[e, 1]] + list(rows[:, 1]),
+                                z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
+                                loops=info["steps_last_run"], reached=info["reached"]))
+            return out
+        finally:
+            batch.close()
+
 
 def _grid_shape(shape):
     """(rows, cols) of a DEM buffer: 2-D as given, 1-D of n*n cells as n x n."""

@@ -304,6 +304,52 @@ int mppi_get_cost_terms(mppi_ctx* ctx, float* terms, int32_t* collisions);
 /* HIP-event time of the last scoring kernel of the context, in milliseconds. */
 int mppi_get_score_ms(mppi_ctx* ctx, double* ms);
 
+/* ---- batched closed-loop episodes ----
+ * MPPI_Controller.run (MPPI_isaac.py:755-806) for E independent episodes at once, the loop's state
+ * feedback done on the GPU: the closed-loop campaigns of the thesis (about 2 000 runs of up to 3 500
+ * steps) and parameter sweeps.  The episodes share the context's scene (DEM, costmap) and
+ * parameters; each has its own start pose, goal, sigmas and Philox seed.  Per step and batch three
+ * launches on the context stream (normals, rollout, finish-and-advance), no host work in between.
+ *
+ * The advance rule after a step (float32 unless noted; v, w = element 0 of the filtered optimal
+ * velocities, row 0 of the optimal rollout, r = params.robot_radius):
+ *   x, y = traj_sim[0]; heading = heading_sim[0] in float64 / sqrt((h0 h0 + h1 h1) + h2 h2), each
+ *   component rounded to float32; ww = (w w) / sigma_div; std_dev_u1 = max(sigma_base, sigma_base -
+ *   ww); std_dev_u2 = max(sigma_base, sigma_base + ww); half = (w r) / 2; left_wheel_speed = v -
+ *   half; right_wheel_speed = v + half; the goal is unchanged.
+ * An episode is active before a step iff |x - goal_x| > goal_tol or |y - goal_y| > goal_tol.
+ * {0.4, 1, 0.5} is run()'s policy (:763-784), {0.25, 3, 0.5} the Isaac loop's
+ * (visual_terrain_stack_full_terrain.py:510-511).  Each step is bitwise the mppi_step of a context
+ * with the episode's seed, state and step index. */
+typedef struct mppi_batch mppi_batch;
+typedef struct mppi_loop_policy {
+  float sigma_base, sigma_div, goal_tol;
+  int32_t check_every;   /* steps enqueued between host looks at the active count; 0 = 16 */
+} mppi_loop_policy;
+/* 1 <= episodes <= 4096; the context's K must give 1 to 16 leaf records of 256 trajectories
+ * (K <= 4096; MPPI_EINVAL otherwise).  The batch borrows the context's scene and parameters at
+ * every run (a DEM or costmap changed between runs is picked up); the context outlives the batch. */
+int  mppi_batch_create(mppi_ctx* ctx, int32_t episodes, mppi_batch** out);
+void mppi_batch_destroy(mppi_batch* b);
+/* Episode e starts at `start` (heading used as given, as mppi_set_state) with Philox key `seed`,
+ * a zero nominal sequence and step index 0, and is runnable; an episode never set does not run. */
+int  mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, uint64_t seed);
+/* Stops the context's resident server, then advances every active episode by up to n_steps steps,
+ * enqueued in chunks of policy->check_every; after each chunk the host waits and reads the count of
+ * active episodes, and stops at 0.  Results do not depend on check_every.  A further call
+ * continues every unfinished episode (the step index keeps counting); the log holds the rows of
+ * the most recent run.  MPPI_ESTATE without a DEM and costmap, or after a HIP error of the batch. */
+int  mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop_policy* policy);
+/* Any output may be NULL.  state: the episode's current state; steps_total: steps since
+ * set_episode; steps_last_run: steps of the most recent run; reached: the goal test has passed;
+ * u1, u2 [H]: the nominal sequence the next step would read. */
+int  mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total,
+                            int32_t* steps_last_run, int32_t* reached, float* u1, float* u2);
+/* rows [count * 8]: x, y, z, the normalised heading, v, w of steps first .. first + count - 1 of the
+ * most recent run (first + count <= steps_last_run). */
+int  mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows);
+int  mppi_batch_get_ms(mppi_batch* b, double* ms);  /* HIP-event time of the last run */
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

@@ -648,6 +648,10 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// a value that is the same in every lane, moved to a scalar register
+__device__ __forceinline__ float uniform_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
 
 // Record combine a (+) b for element j (oracle/mppi_ref.py combine).
 struct __attribute__((aligned(16))) PairScale {  // one 16-byte LDS read
@@ -863,63 +867,83 @@ __device__ __forceinline__ void leaf_records(const RolloutArgs& a, const float* 
   double* red = reinterpret_cast<double*>(scratch + ((TB + NWL) * 4 + 15) / 16 * 16);  // [NL][E]
   // rows (leaf, j), j in [1, E): the pairwise tree over the leaf's 256 trajectories in index
   // order = (half 0) + (half 1), half = ((line 0 + line 1) + (line 2 + line 3)), line = 32
-  // trajectories (8 float4 groups, a pairwise tree of its own).  One LINE per thread and round, its
+  // trajectories (8 float4 groups, a pairwise tree of its own).  A unit is one LINE of one row, its
   // loads issued before any is used: the re-read normals rows come from HBM / MALL (all workgroups'
-  // leaves at once), and the first round's loads are issued before the weights are formed, so their
-  // latency overlaps the weight phase (round 6).  A wave holds 8 rows x 8 lines: lane = 8 k + (row & 7)
-  // for line k of the row, so the eight units of a row sit 8 lanes apart and combine by lane shuffles
-  // (xor 8, 16, 32) in the same order, and the lanes that an LDS read serves together (8 consecutive)
-  // read 8 different rows of the control cache (row stride UCACHE_ROW: 4 banks apart, conflict-free)
-  // or the same weights (a broadcast); with the eight lines of one row in 8 consecutive lanes every
-  // 16-byte read hit the same 4 banks 8 times.
+  // leaves at once).
+  // At the controller's temperature nearly every weight is exactly 0.0f (dm_expf below -87), so a
+  // LIVE MASK per leaf (bit g: the float4 group of trajectories 4 g .. 4 g + 3 holds a non-zero weight;
+  // 16 bits of ballots per weight wave, in the record's unused element red[leaf * E + 0]; byte k =
+  // line k) selects the work:
+  //  * every line live (high temperatures): the DENSE layout, a wave holds 8 rows x 8 lines, lane =
+  //    8 k + (row & 7) for line k of the row, so the eight units of a row sit 8 lanes apart and combine
+  //    by lane shuffles (xor 8, 16, 32) in the tree's order, and the lanes that an LDS read serves
+  //    together (8 consecutive) read 8 different rows of the control cache (row stride UCACHE_ROW:
+  //    4 banks apart, conflict-free) or the same weights (a broadcast).  When the costs already
+  //    tell that every line will be live (`early` below, found by every wave for itself), its first
+  //    round's loads are issued before the weights are formed, so their latency overlaps the weight
+  //    phase (round 6); the mask is then neither formed nor read.
+  //  * otherwise the SPARSE layout: a lane per row (64 rows per wave: the issue slots of a SIMD go
+  //    to one wave's live units, not to sixteen waves' copies of them), each lane looping over the live
+  //    lines only, loading and multiplying their live groups only, and combining the row's line sums
+  //    in registers.  A dead group's or line's true sum is a tree of products 0 * u, u finite: +0 or
+  //    -0.  It is taken as +0.0 unloaded; by induction every node of the tree is then its true value
+  //    or a zero whose true value is a zero too (x + +-0 = x for x != 0), so a row that does not
+  //    compare equal to 0.0 has its true bits.  A row that does (the wrong zero's sign is possible;
+  //    also a leaf with no finite cost) is summed again with every group of every line.
   const int NR = NL * (E - 1);
-  const int NU = ((NR + 7) >> 3) << 6;       // unit slots: 8 rows per wave (the last wave partly empty)
+  const int NU = ((NR + 7) >> 3) << 6;       // dense unit slots: 8 rows per wave (the last wave partly empty)
   struct Unit {
     float4 uq[8];
     int j;
     bool cached;
-    float nom, sg, lo, hi;
-    const float4* w4;
+    int c;      // control 0 / 1 (EPS: selects sigma and the clamp)
+    float nom;
+    int tr0;    // first trajectory of the line
   };
-  auto load = [&](int it, Unit& U) __attribute__((always_inline)) {  // unit slot: row 8 (it >> 6) + (it & 7), line (it >> 3) & 7
-    const int k = (it >> 3) & 7;
-    const int r = min(((it >> 6) << 3) + (it & 7), NR - 1);
-    const int half = k >> 2, line = k & 3;
+  // line k of row r < NR; gm: its float4 groups to load and sum (bit g: trajectories 4 g .. 4 g + 3 of the line)
+  auto load = [&](int r, int k, unsigned gm, Unit& U) __attribute__((always_inline)) {
     const int leaf = r / (E - 1), j = 1 + r - leaf * (E - 1);
     U.j = j;
-    const int tr0 = 256 * leaf + 128 * half + 32 * line;  // first trajectory of the line
-    U.w4 = reinterpret_cast<const float4*>(wbuf + tr0);
+    const int tr0 = 256 * leaf + 32 * k;  // first trajectory of the line
+    U.tr0 = tr0;
     const float4* u4 = reinterpret_cast<const float4*>(ub_block + (size_t)(j >= 2 ? j - 2 : 0) * TB + tr0);
     U.cached = false;  // the sampled controls of this row are in LDS (no normals re-read)
-    U.nom = U.sg = U.lo = U.hi = 0.f;
+    U.nom = 0.f;
+    U.c = 0;
     if constexpr (EPS) {  // rows hold the normals: u = clamp(u_nom[t+1] + sigma*eps) as sampled
       const int c = (j - 2) >= H ? 1 : 0;
       const int t = max(j - 2, 0) - c * H;
       const int ti = min(t + 1, H - 1);
       U.nom = unom[c * H + ti];
-      U.sg = c ? a.s2 : a.s1;
-      U.lo = c ? a.min_u2 : a.min_u1;
-      U.hi = c ? a.max_u2 : a.max_u1;
+      U.c = c;
       if (j >= 2 && t < uc_steps) {
         U.cached = true;
         u4 = reinterpret_cast<const float4*>(ucache + (size_t)(c * uc_steps + t) * UCACHE_ROW + tr0);
       }
     }
 #pragma unroll
-    for (int g = 0; g < 8; ++g) U.uq[g] = (j >= 2) ? u4[g] : make_float4(1.f, 1.f, 1.f, 1.f);
+    for (int g = 0; g < 8; ++g) U.uq[g] = (j >= 2 && ((gm >> g) & 1u)) ? u4[g] : make_float4(1.f, 1.f, 1.f, 1.f);
   };
-  auto reduce = [&](int it, const Unit& U) __attribute__((always_inline)) {
+  auto line_sum = [&](const Unit& U, unsigned gm) __attribute__((always_inline)) {
     const int j = U.j;
+    const float4* w4 = reinterpret_cast<const float4*>(wbuf + U.tr0);
+    const float sg = U.c ? a.s2 : a.s1;
+    const float lo = U.c ? a.min_u2 : a.min_u1;
+    const float hi = U.c ? a.max_u2 : a.max_u1;
     double gs[8];
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-      const float4 w = U.w4[g];
+      if (!((gm >> g) & 1u)) {  // a dead group: +0.0 (below)
+        gs[g] = 0.0;
+        continue;
+      }
+      const float4 w = w4[g];
       float4 u = U.uq[g];
       if (EPS && !U.cached) {
-        u.x = clampf(U.nom + U.sg * u.x, U.lo, U.hi);
-        u.y = clampf(U.nom + U.sg * u.y, U.lo, U.hi);
-        u.z = clampf(U.nom + U.sg * u.z, U.lo, U.hi);
-        u.w = clampf(U.nom + U.sg * u.w, U.lo, U.hi);
+        u.x = clampf(U.nom + sg * u.x, lo, hi);
+        u.y = clampf(U.nom + sg * u.y, lo, hi);
+        u.z = clampf(U.nom + sg * u.z, lo, hi);
+        u.w = clampf(U.nom + sg * u.w, lo, hi);
       }
       if (j < 2) u = make_float4(1.f, 1.f, 1.f, 1.f);  // j == 1: S, the weights alone
       // (w0 u0 + w1 u1) + (w2 u2 + w3 u3) in float64: a product of two floats is exact in a
@@ -929,7 +953,14 @@ __device__ __forceinline__ void leaf_records(const RolloutArgs& a, const float* 
       const double y = __builtin_fma((double)w.z, (double)u.z, (double)w.w * (double)u.w);
       gs[g] = x + y;
     }
-    const double ls = ((gs[0] + gs[1]) + (gs[2] + gs[3])) + ((gs[4] + gs[5]) + (gs[6] + gs[7]));
+    return ((gs[0] + gs[1]) + (gs[2] + gs[3])) + ((gs[4] + gs[5]) + (gs[6] + gs[7]));
+  };
+  // dense unit slot `it`: row 8 (it >> 6) + (it & 7), line (it >> 3) & 7
+  auto dense_load = [&](int it, Unit& U) __attribute__((always_inline)) {
+    load(min(((it >> 6) << 3) + (it & 7), NR - 1), (it >> 3) & 7, 0xffu, U);
+  };
+  auto dense_reduce = [&](int it, const Unit& U) __attribute__((always_inline)) {
+    const double ls = line_sum(U, 0xffu);
     // (line 0 + line 1), (line 2 + line 3): left + right; then the half; then the row
     const double s2 = ls + __shfl_xor(ls, 8, 64);
     const double hs = s2 + __shfl_xor(s2, 16, 64);
@@ -937,29 +968,127 @@ __device__ __forceinline__ void leaf_records(const RolloutArgs& a, const float* 
     const int r = ((it >> 6) << 3) + (it & 7);
     if (r < NR && ((it >> 3) & 7) == 0) {
       const int leaf = r / (E - 1);
-      red[leaf * E + j] = rs;
+      red[leaf * E + U.j] = rs;
     }
   };
-  Unit first;
-  if (tid < NU) load(tid, first);
-  if (wave < NWL) {
-    const float wm = wave_min(cost_lds[tid]);
-    if (lane == 0) wave_m[wave] = wm;
+  // every wave: each leaf's smallest cost from one float4 of costs per lane (lane = four
+  // trajectories, eight lanes = a line), so no wave waits for another's minimum; `early`: every line's
+  // smallest cost is within dm_expf's range of it, so all lines will be live.  (Only a forecast: it
+  // chooses when the dense layout's first loads are issued, the mask comes from the weights.)
+  float lmin[NL];
+  bool early = true;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    const float4 c4 = reinterpret_cast<const float4*>(cost_lds + 256 * q)[lane];
+    const float c = fminf(fminf(c4.x, c4.y), fminf(c4.z, c4.w));
+    const float lo = uniform_f(wave_min(c));
+    lmin[q] = lo;
+    const unsigned long long near = __ballot(c < INFINITY && !(-((c - lo) / a.T) < -87.0f));
+    unsigned long long lines = near | (near >> 4);
+    lines |= lines >> 2;
+    lines |= lines >> 1;  // bit 8 k: a lane of line k is near the minimum
+    early = early && (lines & 0x0101010101010101ull) == 0x0101010101010101ull;
   }
-  __syncthreads();
-  for (int j = tid; j < TB; j += NT) {
-    const int leaf = j >> 8;
-    const float m = fminf(fminf(wave_m[4 * leaf], wave_m[4 * leaf + 1]),
-                          fminf(wave_m[4 * leaf + 2], wave_m[4 * leaf + 3]));
-    const float c = cost_lds[j];
-    wbuf[j] = (c < INFINITY) ? dm_expf(-((c - m) / a.T)) : 0.0f;
-  }
-  __syncthreads();
-  if (tid < NU) reduce(tid, first);
-  for (int it = NT + tid; it < NU; it += NT) {
-    Unit U;
-    load(it, U);
-    reduce(it, U);
+  // the weights, each weight wave's 16 bits of the live mask (mask_tag) and the leaf's minimum for the record
+  auto weights = [&](auto mask_tag) __attribute__((always_inline)) {
+    for (int j = tid; j < TB; j += NT) {  // (whole waves: TB and NT are multiples of 64)
+      const int leaf = j >> 8;
+      float m = lmin[0];
+#pragma unroll
+      for (int q = 1; q < NL; ++q) m = (leaf == q) ? lmin[q] : m;
+      const float c = cost_lds[j];
+      const float w = (c < INFINITY) ? dm_expf(-((c - m) / a.T)) : 0.0f;
+      wbuf[j] = w;
+      if constexpr (!decltype(mask_tag)::value) continue;
+      // trajectories j - lane .. + 63: bit 4 g = group g holds a non-zero weight, then those 16 bits packed
+      unsigned long long gb = __ballot(w != 0.0f);
+      gb |= gb >> 1;
+      gb = (gb | (gb >> 2)) & 0x1111111111111111ull;
+      gb = (gb | (gb >> 3)) & 0x0303030303030303ull;
+      gb = (gb | (gb >> 6)) & 0x000f000f000f000full;
+      gb = (gb | (gb >> 12)) & 0x000000ff000000ffull;
+      gb = (gb | (gb >> 24)) & 0xffffull;
+      if (lane == 0) reinterpret_cast<unsigned short*>(red + leaf * E)[(j >> 6) & 3] = (unsigned short)gb;
+    }
+    if (tid < NWL) {  // (each of the leaf's four slots)
+      float m = lmin[0];
+#pragma unroll
+      for (int q = 1; q < NL; ++q) m = ((tid >> 2) == q) ? lmin[q] : m;
+      wave_m[tid] = m;
+    }
+  };
+  auto dense_rounds = [&](int it0) __attribute__((always_inline)) {
+    for (int it = it0 + tid; it < NU; it += NT) {
+      Unit U;
+      dense_load(it, U);
+      dense_reduce(it, U);
+    }
+  };
+  if (early) {  // (the same in every wave: an arm of its own, so the first unit is live in it alone)
+    Unit first;
+    if (tid < NU) dense_load(tid, first);
+    weights(std::false_type{});
+    __syncthreads();
+    if (tid < NU) dense_reduce(tid, first);
+    dense_rounds(NT);
+  } else {
+    weights(std::true_type{});
+    __syncthreads();
+    // the live groups over the workgroup's leaves (a superset mask is exact too); byte k = line k
+    unsigned long long live = 0ull;
+    bool all_lines = true;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const unsigned long long gq = *reinterpret_cast<const unsigned long long*>(red + q * E);
+      live |= gq;
+      unsigned long long t = gq | (gq >> 4);
+      t |= t >> 2;
+      t |= t >> 1;
+      all_lines = all_lines && (t & 0x0101010101010101ull) == 0x0101010101010101ull;
+    }
+    live = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(live >> 32)) << 32) |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)live);
+    if (all_lines) {  // (uniform: the same words in every lane)
+      dense_rounds(0);
+    } else {
+      const int r = wave * 64 + lane;  // a lane per row: the first (NR + 63) / 64 waves, one per SIMD
+      if (r < NR) {
+        unsigned long long todo = live;
+        double rs;
+        for (;;) {
+          // the lines in order, each node of the tree formed when its right operand arrives (the
+          // pending left operands of the pair, the half and the row: l0, p0, h0)
+          double l0 = 0.0, p0 = 0.0, h0 = 0.0;
+          rs = 0.0;
+#pragma clang loop unroll(disable)
+          for (int k = 0; k < 8; ++k) {
+            const unsigned gm = (unsigned)(todo >> (8 * k)) & 0xffu;
+            double s = 0.0;
+            if (gm) {
+              Unit U;
+              load(r, k, gm, U);
+              s = line_sum(U, gm);
+            }
+            if (!(k & 1)) {
+              l0 = s;
+            } else {
+              const double p = l0 + s;
+              if (!(k & 2)) {
+                p0 = p;
+              } else {
+                const double h = p0 + p;
+                if (!(k & 4)) h0 = h;
+                else rs = h0 + h;
+              }
+            }
+          }
+          if (todo == ~0ull || !(rs == 0.0)) break;
+          todo = ~0ull;  // a zero row: every group of every line, for the sign of the zero
+        }
+        const int leaf = r / (E - 1);
+        red[leaf * E + (1 + r - leaf * (E - 1))] = rs;
+      }
+    }
   }
   __syncthreads();
   for (int j = tid; j < E; j += NT) {
@@ -3442,8 +3571,15 @@ __device__ __forceinline__ const ServerLaunch* fresh_args() {
 #endif
 }
 
+// At most 112 VGPRs (amdgpu_num_vgpr counts the unified file's two halves, 56 + 56): the server's four
+// waves per SIMD never leave, and the deferred optimal rollout (mppi_tail_kernel, 46 -> 48 VGPRs)
+// needs the rest of a SIMD's 512 to run beside them.  At 115 (120 allocated, 32 left) the tail waited
+// for the server's idle exit on every step: 359 launches instead of 3 for 220 steps and half the
+// headline (profiles/leaf_sparse_notes.md).  The cap costs one dword spilled at entry and reloaded
+// once per step, outside the rollout.
 template <int TB, int PROJ>
-__global__ __launch_bounds__(NROLES * TB) void mppi_step_server_kernel(const ServerLaunch args) {
+__global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) void mppi_step_server_kernel(
+    const ServerLaunch args) {
   __shared__ unsigned cmd_lds[32];
   __shared__ int sh[2];
   const int tid = threadIdx.x;

@@ -2,7 +2,8 @@
 // namespace mppi: the kernels are built from its device functions (noise_waves, roles_body,
 // pair_scale / group_apply, finish_phase2) and compute the bits of the single-context step.
 //
-// Three plain stream-ordered launches per step, each with a grid dimension for the episode; an
+// Three plain stream-ordered launches per step (four when the episodes' variants use both
+// projections: one rollout launch each), each with a grid dimension for the episode; an
 // episode's state lives in its BatchEpisode record (device memory), read with wave-uniform loads
 // where a single-context step reads kernel arguments.  No workgroup waits for another or for the
 // host (apart from roles_body's own in-workgroup LDS rings).
@@ -25,7 +26,10 @@ __global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b
 
 // The role-split rollout of leaf block blockIdx.x of episode blockIdx.y: the launch's RolloutArgs
 // (scene and parameters) with the episode's state, derived critic fields, seed, Philox base and
-// buffer slices patched in.
+// buffer slices patched in, and, for an episode that holds a variant, its row of the table
+// (BatchArgs::var) over the parameters a variant may override.  With a table the launch serves the
+// episodes of projection PROJ only (the row's, or the run's for an episode without a variant): a
+// workgroup of another projection's episode returns at once, like an inactive one.
 template <int PROJ>
 __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const RolloutArgs a_in, const BatchArgs b) {
   const int e = blockIdx.y;
@@ -33,6 +37,24 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
   if (!ep->active) return;
   RolloutArgs a = a_in;
   const int H = a.H;
+  if (b.var) {  // (null: no episode holds a variant, and the launch is the run's projection)
+    const int vi = b.ep_var[e];
+    if (vi >= 0) {
+      const BatchVariant* v = b.var + vi;
+      if (v->proj != PROJ) return;
+      a.w_path = v->w_path;
+      a.w_slope = v->w_slope;
+      a.w_speed = v->w_speed;
+      a.w_obs = v->w_obs;
+      a.thr = v->thr;
+      a.pen = v->pen;
+      a.T = v->T;  // leaf_records (its dense / sparse forecast included) reads a.T only
+      a.fk = v->fk;
+      a.fa = v->fa;
+    } else if (b.proj != PROJ) {
+      return;
+    }
+  }
   a.x0 = ep->x0;
   a.y0 = ep->y0;
   a.h0x = ep->h0x;
@@ -74,6 +96,18 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   const int tid = threadIdx.x;
   FinishArgs f = f_in;
   const int H = f.H, E = 2 * H + 2;
+  float sigma_base = b.sigma_base, sigma_div = b.sigma_div;
+  if (b.var) {
+    const int vi = b.ep_var[e];
+    if (vi >= 0) {
+      const BatchVariant* v = b.var + vi;
+      f.T = v->T;
+      f.ok = v->ok;
+      f.oa = v->oa;
+      sigma_base = v->sigma_base;
+      sigma_div = v->sigma_div;
+    }
+  }
   const int cur_buf = ep->cur;
   const float gx = ep->gx, gy = ep->gy;
   const int row = ep->steps_run;
@@ -150,7 +184,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     lg[6] = v;
     lg[7] = w;
   }
-  const float ww = (w * w) / b.sigma_div;
+  const float ww = (w * w) / sigma_div;
   const float half = (w * b.rwheel) / 2.0f;
   ep->x0 = x;
   ep->y0 = y;
@@ -159,8 +193,8 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   ep->h0z = hz;
   ep->wl = v - half;
   ep->wr = v + half;
-  ep->s1 = fmaxf(b.sigma_base, b.sigma_base - ww);
-  ep->s2 = fmaxf(b.sigma_base, b.sigma_base + ww);
+  ep->s1 = fmaxf(sigma_base, sigma_base - ww);
+  ep->s2 = fmaxf(sigma_base, sigma_base + ww);
   {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
     const float xd = gx - x;
     const float yd = gy - y;

@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>  // types only: RCCL is opened with dlopen by mppi_group_create
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <chrono>
@@ -1786,6 +1787,25 @@ int mppi_dump_rollouts(mppi_ctx* c, float* traj, float* hv, float* lw, float* rw
 // ---- path scoring (mppi_score.hip) ----
 namespace {
 
+// One launch of the scoring kernel on the context stream, bracketed by HIP events (score_ms).  Waits
+// for the stream.
+int run_score(mppi_ctx* c, const ScoreArgs& a) {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+  if (e == hipSuccess) e = launch_score(a, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev)
+    if (x) hipEventDestroy(x);
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("score: ") + hipGetErrorString(e));
+  c->score_ms = ms;
+  return MPPI_OK;
+}
+
 // Score n device-resident paths of `stride` waypoints from `st` (x, y, goal) with the context's
 // costmap and critic parameters; the kernel is bracketed by HIP events (score_ms).  Waits for the stream.
 int score_device(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* lengths, const float* traj,
@@ -1824,20 +1844,7 @@ int score_device(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* lengths,
   a.cost = cost;
   a.terms = terms;
   a.collisions = collisions;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = launch_score(a, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  float ms = 0.0f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  for (hipEvent_t x : ev)
-    if (x) hipEventDestroy(x);
-  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("score: ") + hipGetErrorString(e));
-  c->score_ms = ms;
-  return MPPI_OK;
+  return run_score(c, a);
 }
 
 size_t up16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
@@ -2830,9 +2837,36 @@ struct mppi_batch {
   hipEvent_t ev[2] = {nullptr, nullptr};
   double last_ms = 0;
   bool failed = false;  // a HIP error of the batch: further runs are refused
+  // per-episode parameter variants (mppi_batch_set_variants / _set_episode_variant)
+  std::vector<mppi_batch_variant> variants;  // the table as last set
+  std::vector<int> ep_var;                   // [E] each episode's row, -1: none
+  BatchVariant* d_var = nullptr;             // [kBatchMaxVariants]
+  int* d_ep_var = nullptr;                   // [E]
+  // [E] x, y, goal_x, goal_y of each episode when its most recent run began (mppi_batch_score)
+  std::vector<std::array<float, 4>> origin;
 };
+static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
 
 namespace {
+
+BatchVariant device_variant(const mppi_batch_variant& v) {
+  BatchVariant r;
+  r.w_path = v.w_path;
+  r.w_slope = v.w_slope;
+  r.w_speed = v.w_speed;
+  r.w_obs = v.w_obstacle;
+  r.thr = v.collision_threshold;
+  r.pen = v.collision_penalty;
+  r.T = v.temperature;
+  r.fk = v.filter_k;
+  r.fa = v.filter_a;
+  r.ok = v.opt_filter_k;
+  r.oa = v.opt_filter_a;
+  r.sigma_base = v.sigma_base;
+  r.sigma_div = v.sigma_div;
+  r.proj = v.proj;
+  return r;
+}
 
 int batch_episode(mppi_batch* b, int32_t e) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
@@ -2858,8 +2892,16 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   int rc = batch_pull(b);
   if (rc) return rc;
   int active = 0;
+  // the projections in use: a set episode's variant's, or the run's where it holds none
+  bool any_var = false, use_proj[4] = {false, false, false, false};
   for (int e = 0; e < b->E; ++e) {
     BatchEpisode& r = b->host[e];
+    b->origin[e] = {r.x0, r.y0, r.gx, r.gy};
+    if (b->is_set[e]) {
+      const int vi = b->ep_var[e];
+      any_var = any_var || vi >= 0;
+      use_proj[vi >= 0 ? b->variants[vi].proj : proj] = true;
+    }
     r.steps_run = 0;
     const bool outside = std::fabs(r.x0 - r.gx) > pol.goal_tol || std::fabs(r.y0 - r.gy) > pol.goal_tol;
     r.active = b->is_set[e] && outside ? 1 : 0;
@@ -2893,6 +2935,9 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   fill_finish(c, pl, none, f);
   f.mode = 2;
   BatchArgs z{};
+  z.var = any_var ? b->d_var : nullptr;  // null: the kernels of the batch without variants
+  z.ep_var = b->d_ep_var;
+  z.proj = proj;
   z.ep = b->ep;
   z.E = b->E;
   z.blocks = b->blocks;
@@ -2917,7 +2962,10 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
     const int m = std::min(every, n_steps - done);
     for (int i = 0; i < m; ++i) {
       HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
-      HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, proj));
+      // one rollout launch per projection in use (a workgroup of the other projection's episode
+      // returns at once); without variants that is the run's projection alone
+      for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
+        if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
       HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2954,7 +3002,13 @@ int mppi_batch_create(mppi_ctx* c, int32_t episodes, mppi_batch** out) {
   const size_t E = (size_t)episodes;
   b->host.assign(E, BatchEpisode{});
   b->is_set.assign(E, 0);
+  b->ep_var.assign(E, -1);
+  b->origin.assign(E, std::array<float, 4>{0.0f, 0.0f, 0.0f, 0.0f});
   if (hipMalloc(&b->ep, E * sizeof(BatchEpisode)) != hipSuccess ||
+      hipMalloc(&b->d_var, kBatchMaxVariants * sizeof(BatchVariant)) != hipSuccess ||
+      hipMalloc(&b->d_ep_var, E * sizeof(int)) != hipSuccess ||
+      hipMemset(b->d_var, 0, kBatchMaxVariants * sizeof(BatchVariant)) != hipSuccess ||
+      hipMemset(b->d_ep_var, 0xff, E * sizeof(int)) != hipSuccess ||
       hipMalloc(&b->eps, E * blocks * 2 * H * 256 * sizeof(float)) != hipSuccess ||
       hipMalloc(&b->unom, E * 4 * H * sizeof(float)) != hipSuccess ||
       hipMalloc(&b->nodes, E * blocks * (2 * H + 2) * sizeof(double)) != hipSuccess ||
@@ -2981,6 +3035,8 @@ void mppi_batch_destroy(mppi_batch* b) {
   hipSetDevice(b->c->device);
   if (b->c->stream) hipStreamSynchronize(b->c->stream);
   if (b->ep) hipFree(b->ep);
+  if (b->d_var) hipFree(b->d_var);
+  if (b->d_ep_var) hipFree(b->d_ep_var);
   if (b->eps) hipFree(b->eps);
   if (b->unom) hipFree(b->unom);
   if (b->nodes) hipFree(b->nodes);
@@ -3098,6 +3154,153 @@ int mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, f
 int mppi_batch_get_ms(mppi_batch* b, double* ms) {
   if (!b || !ms) return fail(MPPI_EINVAL, "null argument");
   *ms = b->last_ms;
+  return MPPI_OK;
+}
+
+int mppi_batch_variant_default(mppi_batch* b, int32_t proj, const mppi_loop_policy* policy,
+                               mppi_batch_variant* out) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!policy || !out) return fail(MPPI_EINVAL, "null argument");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  const mppi_params& p = b->c->p;
+  out->w_path = p.w_path;
+  out->w_slope = p.w_slope;
+  out->w_speed = p.w_speed;
+  out->w_obstacle = p.w_obstacle;
+  out->collision_threshold = p.collision_threshold;
+  out->collision_penalty = p.collision_penalty;
+  out->temperature = p.temperature;
+  out->filter_k = p.filter_k;
+  out->filter_a = p.filter_a;
+  out->opt_filter_k = p.opt_filter_k;
+  out->opt_filter_a = p.opt_filter_a;
+  out->sigma_base = policy->sigma_base;
+  out->sigma_div = policy->sigma_div;
+  out->proj = proj;
+  return MPPI_OK;
+}
+
+int mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant* v) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (n < 0 || n > kBatchMaxVariants) return fail(MPPI_EINVAL, "variants: n must be in [0, 1024]");
+  if (n > 0 && !v) return fail(MPPI_EINVAL, "null argument");
+  for (int i = 0; i < n; ++i) {
+    const std::string row = "variant row " + std::to_string(i) + ": ";
+    // the checks of mppi_create on the fields a variant overrides, and the run's on sigma_div / proj
+    if (!(v[i].temperature > 0.0f)) return fail(MPPI_EINVAL, row + "temperature must be > 0");
+    if (!(v[i].sigma_div != 0.0f)) return fail(MPPI_EINVAL, row + "sigma_div must be non-zero");
+    if (v[i].proj != MPPI_PROJ_2D && v[i].proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, row + "proj must be 2 or 3");
+  }
+  for (int e = 0; e < b->E; ++e)
+    if (b->ep_var[e] >= n)
+      return fail(MPPI_EINVAL, "variants: episode " + std::to_string(e) + " holds row " +
+                                   std::to_string(b->ep_var[e]) + " of the table, n = " + std::to_string(n));
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<BatchVariant> rows((size_t)n);
+  for (int i = 0; i < n; ++i) rows[i] = device_variant(v[i]);
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(b->d_var, rows.data(), (size_t)n * sizeof(BatchVariant), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // rows is pageable and dies here
+  }
+  b->variants.assign(v, v + n);
+  return MPPI_OK;
+}
+
+int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (variant < -1 || variant >= (int32_t)b->variants.size())
+    return fail(MPPI_EINVAL, "variant index " + std::to_string(variant) + " outside the table of " +
+                                 std::to_string(b->variants.size()) + " rows");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  b->ep_var[e] = variant;
+  HIP_TRY(hipMemcpyAsync(b->d_ep_var + e, &b->ep_var[e], sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                     mppi_path_scores* out, int32_t* rows) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!out) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (!c->cm) return fail(MPPI_ESTATE, "batch_score: no costmap: call mppi_set_costmap first");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t E = (size_t)b->E;
+  if (!b->log) {  // no run yet: no episode has a row
+    if (out->cost) std::memset(out->cost, 0, E * 4);
+    if (out->terms) std::memset(out->terms, 0, E * 16);
+    if (out->collisions) std::memset(out->collisions, 0, E * 4);
+    if (rows) std::memset(rows, 0, E * 4);
+    return MPPI_OK;
+  }
+  const mppi_params& p = c->p;
+  std::vector<ScoreGoal> goals(E);
+  for (size_t e = 0; e < E; ++e) {
+    mppi_state st{};
+    if (origins) {
+      st.x = origins[e].x;
+      st.y = origins[e].y;
+      st.goal_x = origins[e].goal_x;
+      st.goal_y = origins[e].goal_y;
+    } else {
+      st.x = b->origin[e][0];
+      st.y = b->origin[e][1];
+      st.goal_x = b->origin[e][2];
+      st.goal_y = b->origin[e][3];
+    }
+    ServerCmd d;
+    state_fields(p, st, d);
+    goals[e] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
+  }
+  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows]
+  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16;
+  char* buf = nullptr;
+  HIP_TRY(hipMalloc(&buf, bg + bn * 3 + bt));
+  ScoreGoal* d_goals = (ScoreGoal*)buf;
+  float* d_cost = (float*)(buf + bg);
+  float* d_terms = (float*)(buf + bg + bn);
+  int32_t* d_col = (int32_t*)(buf + bg + bn + bt);
+  int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
+  ScoreArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.log = b->log;
+  a.goals = d_goals;
+  a.lengths = &b->ep->steps_run;  // the episode table's own counters, one record apart
+  a.len_step = (int)(sizeof(BatchEpisode) / sizeof(int32_t));
+  a.rows_out = d_rows;
+  a.n = (int64_t)E;
+  a.stride = b->log_cap;
+  a.cm = c->cm;
+  a.cm_size = c->cm_size;
+  a.hw = c->cm_hw;
+  a.res_c = c->cm_res;
+  a.vmax = p.v_max_linear;
+  a.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+  a.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+  a.w_path = yardstick ? yardstick->w_path : p.w_path;
+  a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+  a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+  a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  a.cost = d_cost;
+  a.terms = d_terms;
+  a.collisions = d_col;
+  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
+  int rc = MPPI_OK;
+  if (e == hipSuccess) rc = run_score(c, a);
+  if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, E * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && rows) e = hipMemcpyAsync(rows, d_rows, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  hipFree(buf);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("batch_score: ") + hipGetErrorString(e));
   return MPPI_OK;
 }
 

@@ -209,7 +209,21 @@ struct BatchEpisode {
   int reached;     // the goal test passed
 };
 static_assert(sizeof(BatchEpisode) == 96, "BatchEpisode layout");
+// One row of the batch's variant table: mppi_batch_variant (include/mppi.h) field for field.  The
+// parameters an episode may override: kernel scalars only, read with wave-uniform loads.
+struct BatchVariant {
+  float w_path, w_slope, w_speed, w_obs, thr, pen, T, fk, fa, ok, oa, sigma_base, sigma_div;
+  int proj;
+};
+static_assert(sizeof(BatchVariant) == 56, "BatchVariant layout");
+constexpr int kBatchMaxVariants = 1024;
 struct BatchArgs {
+  // null when no set episode holds a variant: the kernels then read no table, and a batch without
+  // variants runs as it did before there were any (the index and the row are two dependent loads
+  // at the head of the rollout and of the finish: 0.6 us per step measured at K = 1 000, E = 64)
+  const BatchVariant* var;  // [kBatchMaxVariants] the variant table
+  const int* ep_var;        // [E] each episode's row of the table, -1: none
+  int proj;                 // the run's projection: that of the episodes without a variant
   BatchEpisode* ep;  // [E]
   int E, blocks, H;
   int64_t k_pad;     // blocks * 256
@@ -221,7 +235,7 @@ struct BatchArgs {
                      // tail inputs [3H] (written by finish_phase2, not read: the loop consumes row 0 only)
   float* log;        // [E][log_cap][8]: x, y, z, heading, v, w per step of the run
   int log_cap;
-  float sigma_base, sigma_div, goal_tol;  // mppi_loop_policy
+  float sigma_base, sigma_div, goal_tol;  // mppi_loop_policy (an episode's variant overrides the sigmas)
   float horizon, rwheel;                  // mppi_params horizon, robot_radius
   int* active_count;                      // pinned host memory: episodes still active
 };

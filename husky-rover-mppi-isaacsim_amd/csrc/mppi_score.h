@@ -16,13 +16,28 @@ constexpr int SCORE_PATHS = 64;
 constexpr int SCORE_CHUNK = 12;
 constexpr int SCORE_THREADS = 256;
 
+// The goal terms of one path where every path has its own origin and goal (the episodes of a batch):
+// state_fields() of mppi_capi.cpp, computed on the host.
+struct ScoreGoal {
+  float gx, gy, igx, igy, pf_scale;
+  int pf_far, speed_on, pad;
+};
+static_assert(sizeof(ScoreGoal) == 32, "ScoreGoal layout");
+
 struct ScoreArgs {
   // paths, trajectory-major (device memory)
-  const float* traj;       // [n][stride][3]
+  const float* traj;       // [n][stride][3]; with `log`: not read
   const float* lw;         // [n][stride][3] or null (then rw is null too: the slope critic reads traj)
   const float* rw;
   const float* v;          // [n][stride]
   const int32_t* lengths;  // [n], each in [1, stride], or null (every path has stride waypoints)
+  // the log of a batch (mppi_batch_score) instead of traj / v: [n][stride][8] rows x, y, z, heading, v, w,
+  // 32-byte aligned; then lw = rw = null, lengths[p * len_step] (>= 0, clamped to stride) is path p's
+  // length, goals [n] replaces gx .. speed_on below, and rows_out [n] (or null) receives the lengths
+  const float* log;
+  const ScoreGoal* goals;
+  int len_step;
+  int32_t* rows_out;
   int64_t n;
   int stride;              // n * stride < 2^31
   // costmap (critics_warp.py:244-248)

@@ -22,7 +22,18 @@
 //          SIMDs busy with 64 paths per workgroup.
 // The chunk loop runs to the longest path of the tile, whatever the stride: LDS use does not depend
 // on the path length.  Rows past a path's length are staged but never enter a chain.
+//
+// LOG instantiation (mppi_batch_score): the paths are the rows of a batch's log, [path][stride][8]
+// floats (x, y, z, heading, v, w), each path with its own goal terms (ScoreGoal).  A waypoint is one
+// 32-byte row, so a thread takes whole waypoints: one aligned 16-byte load (x, y, z and a heading
+// component it drops) and the 4 bytes of v, 3 waypoints per thread and chunk; a chunk of one path
+// is 12 x 32 contiguous bytes and consecutive lanes read consecutive rows.  Only x, y, z, v are
+// staged, into the same LDS rows (strides 37 and 13), so the score phase is the same code; pf_far
+// and speed_on become per-lane branches.
 #include "mppi_score.h"
+
+#include <algorithm>
+#include <type_traits>
 
 namespace mppi {
 
@@ -86,6 +97,49 @@ __device__ __forceinline__ void stage_array(const float* __restrict__ g, float (
   }
 }
 
+// LOG: the chunk in flight, x, y, z, v of the thread's waypoints.
+constexpr int LOG_WP = TP * CT / NT;
+static_assert(LOG_WP * NT == TP * CT, "whole waypoints per thread");
+struct StageLog {
+  float q[LOG_WP][4];
+};
+
+// Waypoint u of the tile = row t0 + u % len of path p0 + u / len.
+template <bool STORE>
+__device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
+                                                int tid) {
+  const bool full = len == CT;
+  const int total = TP * len;
+#pragma unroll
+  for (int i = 0; i < LOG_WP; ++i) {
+    const int u = tid + i * NT;
+    if (u >= total) continue;
+    const int pp = full ? u / CT : u / len;
+    const int tt = u - pp * len;
+    if (p0 + pp >= a.n) continue;
+    if constexpr (!STORE) {
+      const float* src = a.log + ((size_t)(p0 + pp) * (size_t)a.stride + (size_t)(t0 + tt)) * 8;
+      const float4 xyz = *reinterpret_cast<const float4*>(src);
+      r.q[i][0] = xyz.x;
+      r.q[i][1] = xyz.y;
+      r.q[i][2] = xyz.z;
+      r.q[i][3] = src[6];
+    } else {
+      float* dst = sm.a[0] + pp * ROW3 + 3 * tt;
+      dst[0] = r.q[i][0];
+      dst[1] = r.q[i][1];
+      dst[2] = r.q[i][2];
+      sm.v[pp * ROWV + tt] = r.q[i][3];
+    }
+  }
+}
+
+template <int VEC, bool WHEELS, bool STORE>
+__device__ __forceinline__ void stage_chunk(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
+                                            int tid) {
+  stage_chunk_log<STORE>(a, r, sm, p0, t0, len, tid);
+}
+
 template <int VEC, bool WHEELS, bool STORE>
 __device__ __forceinline__ void stage_chunk(const ScoreArgs& a, Stage<VEC>& r, Smem& sm, int64_t p0, int t0, int len,
                                             int tid) {
@@ -118,15 +172,21 @@ __device__ __forceinline__ int cm_index(const ScoreArgs& a, float x, float y) {
   return ix + a.cm_size * iy;
 }
 
-template <int VEC, bool WHEELS>
+// LOG: the paths are a batch's log with per-path goal terms (see above); VEC = 1, WHEELS = false there.
+template <int VEC, bool WHEELS, bool LOG = false>
 __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
+  static_assert(!LOG || (VEC == 1 && !WHEELS), "the log loader takes whole rows and has no wheel arrays");
   __shared__ Smem sm;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int role = tid >> 6;  // wave-uniform: 0 path, 1 slope, 2 speed, 3 obstacle
   const int64_t p0 = (int64_t)blockIdx.x * TP;
   const int64_t p = p0 + lane;
-  const int L = p < a.n ? (a.lengths ? min(a.lengths[p], a.stride) : a.stride) : 0;
+  int L;
+  if constexpr (LOG)
+    L = p < a.n ? min(max(a.lengths[(size_t)p * a.len_step], 0), a.stride) : 0;
+  else
+    L = p < a.n ? (a.lengths ? min(a.lengths[p], a.stride) : a.stride) : 0;
   int Lmax = L;  // the tile's longest path: the same value in every wave
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) Lmax = max(Lmax, __shfl_xor(Lmax, o, 64));
@@ -138,7 +198,26 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
   int col = 0;
   float pl[3] = {0.0f, 0.0f, 0.0f}, pr[3] = {0.0f, 0.0f, 0.0f};  // slope: the previous even waypoint
 
-  Stage<VEC> r;
+  // the goal terms: kernel arguments, or (LOG) the lane's own path's, each wave loading its critic's
+  float gx = a.gx, gy = a.gy, igx = a.igx, igy = a.igy, pf_scale = a.pf_scale;
+  int pf_far = a.pf_far, speed_on = a.speed_on;
+  if constexpr (LOG) {
+    if (p < a.n) {
+      const ScoreGoal* g = a.goals + p;
+      if (role == 0) {
+        gx = g->gx;
+        gy = g->gy;
+        igx = g->igx;
+        igy = g->igy;
+        pf_scale = g->pf_scale;
+        pf_far = g->pf_far;
+      } else if (role == 2) {
+        speed_on = g->speed_on;
+      }
+    }
+  }
+
+  std::conditional_t<LOG, StageLog, Stage<VEC>> r;
   stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, 0, min(CT, Lld), tid);
   stage_chunk<VEC, WHEELS, true>(a, r, sm, p0, 0, min(CT, Lld), tid);
   __syncthreads();
@@ -151,17 +230,17 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     const int te = min(t0 + len, L);  // this lane's waypoints of the chunk: [t0, te)
     if (role == 0) {
       const float* q = sm.a[0] + lane * ROW3;
-      if (a.pf_far) {  // critics_warp.py:111-119: the terminal waypoint against the intermediate goal
+      if (pf_far) {  // critics_warp.py:111-119: the terminal waypoint against the intermediate goal
         const int tl = L - 1;
         if (tl >= t0 && tl < te) {
-          const float dx = q[3 * (tl - t0)] - a.igx;
-          const float dy = q[3 * (tl - t0) + 1] - a.igy;
-          acc = (dx * dx + dy * dy) * a.pf_scale;
+          const float dx = q[3 * (tl - t0)] - igx;
+          const float dy = q[3 * (tl - t0) + 1] - igy;
+          acc = (dx * dx + dy * dy) * pf_scale;
         }
       } else {  // :120-123
         const int tp = min(te, L - 1);
         for (int t = t0; t < tp; ++t)
-          acc = acc + 10.0f * (fabsf(q[3 * (t - t0)] - a.gx) + fabsf(q[3 * (t - t0) + 1] - a.gy));
+          acc = acc + 10.0f * (fabsf(q[3 * (t - t0)] - gx) + fabsf(q[3 * (t - t0) + 1] - gy));
       }
     } else if (role == 1) {
       const float* ql = sm.a[WHEELS ? 1 : 0] + lane * ROW3;
@@ -190,7 +269,7 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
         }
       }
     } else if (role == 2) {
-      if (a.speed_on) {  // critics_warp.py:281-300
+      if (speed_on) {  // critics_warp.py:281-300
         const float* q = sm.v + lane * ROWV;
         for (int t = t0; t < te; ++t) {
           const float vt = q[t - t0];
@@ -226,9 +305,13 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
       cost = cost + a.w_slope * sw;
       cost = cost + a.w_speed * sp;
       cost = cost + a.w_obs * ob;
+      if constexpr (LOG)
+        if (L == 0) cost = 0.0f;  // an episode with no rows: cost 0 whatever the weights
       a.cost[p] = cost;
     }
     if (a.collisions) a.collisions[p] = sm.col[lane];
+    if constexpr (LOG)
+      if (a.rows_out) a.rows_out[p] = L;
   }
 }
 
@@ -238,6 +321,15 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 hipError_t launch_score(const ScoreArgs& a, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
+  if (a.log) {
+    // stride 0: no run yet, every length is clamped to 0 and no row is read
+    if (!a.goals || !a.lengths || !a.cm || a.lw || a.rw || a.stride < 0 || a.cm_size < 1 || a.len_step < 1 ||
+        ((uintptr_t)a.log & 31) != 0 || (a.terms && !aligned16(a.terms)) ||
+        a.n * (int64_t)std::max(a.stride, 1) >= ((int64_t)1 << 31))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL((mppi_score_kernel<1, false, true>), dim3((unsigned)((a.n + TP - 1) / TP)), dim3(NT), 0, st, a);
+    return hipGetLastError();
+  }
   if (!a.traj || !a.v || !a.cm || a.stride < 1 || a.cm_size < 1 || (a.lw == nullptr) != (a.rw == nullptr) ||
       (a.terms && !aligned16(a.terms)) || a.n * (int64_t)a.stride >= ((int64_t)1 << 31))
     return hipErrorInvalidValue;

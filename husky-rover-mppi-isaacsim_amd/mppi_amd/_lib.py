@@ -73,6 +73,15 @@ class MppiLoopPolicy(C.Structure):
                 ("check_every", C.c_int32)]
 
 
+VARIANT_FIELDS = ("w_path", "w_slope", "w_speed", "w_obstacle", "collision_threshold", "collision_penalty",
+                  "temperature", "filter_k", "filter_a", "opt_filter_k", "opt_filter_a", "sigma_base", "sigma_div")
+
+
+class MppiBatchVariant(C.Structure):
+    """mppi_batch_variant: the parameters one episode of a batch may override (56 bytes)."""
+    _fields_ = [(n, C.c_float) for n in VARIANT_FIELDS] + [("proj", C.c_int32)]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
 
 
@@ -145,6 +154,12 @@ _PROTOS = {
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, _FP]),
     "mppi_batch_get_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "mppi_batch_get_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mppi_batch_variant_default": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiLoopPolicy),
+                                             C.POINTER(MppiBatchVariant)]),
+    "mppi_batch_set_variants": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchVariant)]),
+    "mppi_batch_set_episode_variant": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mppi_batch_score": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
+                                   C.POINTER(MppiPathScores), C.POINTER(C.c_int32)]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
                                          C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_int32)]),
 }
@@ -624,6 +639,33 @@ def make_policy(sigma_base=0.4, sigma_div=1.0, goal_tol=0.5, check_every=0):
     return MppiLoopPolicy(float(sigma_base), float(sigma_div), float(goal_tol), int(check_every))
 
 
+def make_variant(proj="3d", **fields):
+    """Fill mppi_batch_variant: the defaults of make_params and run()'s sigma schedule, overridden by
+    `fields` (VARIANT_FIELDS); float fields are rounded to float32 by ctypes.  A dict (as
+    Batch.variant_default returns or mppi_amd.batch.variant_params takes) passes as **dict."""
+    unknown = set(fields) - set(VARIANT_FIELDS)
+    if unknown:
+        raise ValueError(f"not fields of mppi_batch_variant: {sorted(unknown)}")
+    p = make_params(1, 1)
+    v = MppiBatchVariant()
+    for n in VARIANT_FIELDS:
+        default = {"sigma_base": 0.4, "sigma_div": 1.0}.get(n)
+        setattr(v, n, float(fields.get(n, getattr(p, n) if default is None else default)))
+    v.proj = PROJ[proj]
+    return v
+
+
+def variant_as_dict(v: MppiBatchVariant):
+    """The dict of a MppiBatchVariant (what mppi_amd.batch.variant_params takes)."""
+    d = {n: np.float32(getattr(v, n)) for n in VARIANT_FIELDS}
+    d["proj"] = int(v.proj)
+    return d
+
+
+def _as_variant(v):
+    return v if isinstance(v, MppiBatchVariant) else make_variant(**dict(v))
+
+
 class Batch:
     """mppi_batch (include/mppi.h): E closed-loop episodes over one Engine's scene and parameters,
     advanced on the GPU with no host work between steps.  Keeps a reference to its Engine, so the
@@ -638,10 +680,52 @@ class Batch:
         _check(self.lib, self.lib.mppi_batch_create(engine.ctx, self.E, C.byref(h)), "mppi_batch_create")
         self.h = h
 
-    def set_episode(self, e, state: MppiState, seed):
+    def set_episode(self, e, state: MppiState, seed, variant=-1):
+        """Episode e starts at `state` with Philox key `seed` and runs with row `variant` of the table
+        of set_variants (-1: the engine's params and run()'s proj / policy)."""
         _check(self.lib, self.lib.mppi_batch_set_episode(self.h, int(e), C.byref(state),
                                                          int(seed) & 0xFFFFFFFFFFFFFFFF),
                "mppi_batch_set_episode")
+        _check(self.lib, self.lib.mppi_batch_set_episode_variant(self.h, int(e), int(variant)),
+               "mppi_batch_set_episode_variant")
+
+    def set_variants(self, variants):
+        """The batch's variant table: a list of MppiBatchVariant or dicts (make_variant's arguments);
+        an empty list clears it."""
+        rows = [_as_variant(v) for v in variants]
+        arr = (MppiBatchVariant * max(len(rows), 1))(*rows)
+        _check(self.lib, self.lib.mppi_batch_set_variants(self.h, len(rows), arr), "mppi_batch_set_variants")
+
+    def variant_default(self, proj="3d", policy=None):
+        """The variant that changes nothing: the engine's params with `proj` and the policy's sigma schedule."""
+        pol = policy if policy is not None else make_policy()
+        v = MppiBatchVariant()
+        _check(self.lib, self.lib.mppi_batch_variant_default(self.h, PROJ[proj], C.byref(pol), C.byref(v)),
+               "mppi_batch_variant_default")
+        return v
+
+    def score(self, yardstick=None, origins=None):
+        """mppi_batch_score: every episode's executed path (the log of its most recent run) scored on
+        the device with one cost function.  yardstick: MppiBatchVariant or dict whose weights,
+        collision_threshold and collision_penalty are used (default the engine's params); origins: E
+        MppiState (x, y, goal_x, goal_y are read; default each episode's position when its most recent
+        run began and its goal).  Returns dict(cost [E], terms [E, 4] in COST_TERMS order,
+        collisions [E], rows [E])."""
+        E = self.E
+        out = dict(cost=np.zeros(E, np.float32), terms=np.zeros((E, 4), np.float32),
+                   collisions=np.zeros(E, np.int32), rows=np.zeros(E, np.int32))
+        i32 = C.POINTER(C.c_int32)
+        sc = MppiPathScores(_fp(out["cost"]), _fp(out["terms"]), out["collisions"].ctypes.data_as(i32))
+        y = None if yardstick is None else C.byref(_as_variant(yardstick))
+        o = None
+        if origins is not None:
+            origins = list(origins)
+            if len(origins) != E:
+                raise ValueError(f"{E} episodes but {len(origins)} origins")
+            o = (MppiState * E)(*origins)
+        _check(self.lib, self.lib.mppi_batch_score(self.h, y, o, C.byref(sc), out["rows"].ctypes.data_as(i32)),
+               "mppi_batch_score")
+        return out
 
     def run(self, n_steps, proj="3d", policy=None):
         """Advance every active episode by up to n_steps steps (policy: MppiLoopPolicy, default run()'s)."""

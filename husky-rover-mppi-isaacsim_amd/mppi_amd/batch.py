@@ -20,6 +20,60 @@ STATE_FIELDS = ("x", "y", "heading", "left_wheel_speed", "right_wheel_speed", "g
                 "std_dev_u1", "std_dev_u2")
 
 
+# mppi_batch_variant (include/mppi.h): the mppi_params fields a variant overrides, then the loop
+# policy's sigma schedule and the projection
+VARIANT_PARAM_FIELDS = ("w_path", "w_slope", "w_speed", "w_obstacle", "collision_threshold", "collision_penalty",
+                        "temperature", "filter_k", "filter_a", "opt_filter_k", "opt_filter_a")
+VARIANT_POLICY_FIELDS = ("sigma_base", "sigma_div")
+
+
+def variant_params(params, variant, policy=None, proj="3d"):
+    """What an episode that holds `variant` runs with: (params dict, policy dict, proj).
+
+    params: the batch context's parameters by mppi_params field name (any mapping; fields not
+    given keep the library's defaults when passed on to make_params); variant: dict of
+    mppi_batch_variant fields, or None for an episode without a variant; policy, proj: those of
+    mppi_batch_run.  Exactly VARIANT_PARAM_FIELDS are overridden in params, sigma_base / sigma_div in
+    the policy (goal_tol and check_every stay the run's), and proj by the variant's ("2d" / "3d" or
+    2 / 3).  A variant must give every field, as the C struct does; Batch.variant_default or
+    _lib.make_variant fill them.
+    """
+    out = dict(params)
+    pol = dict(policy or RUN_POLICY)
+    if variant is None:
+        return out, pol, proj
+    v = dict(variant)
+    known = set(VARIANT_PARAM_FIELDS) | set(VARIANT_POLICY_FIELDS) | {"proj"}
+    if set(v) != known:
+        raise ValueError(f"a variant gives exactly {sorted(known)}; got {sorted(v)}")
+    for k in VARIANT_PARAM_FIELDS:
+        out[k] = F32(v[k])
+    for k in VARIANT_POLICY_FIELDS:
+        pol[k] = F32(v[k])
+    if not pol["sigma_div"] != 0:
+        raise ValueError("sigma_div must be non-zero")
+    if not out["temperature"] > 0:
+        raise ValueError("temperature must be > 0")
+    pj = {2: "2d", 3: "3d", "2d": "2d", "3d": "3d"}.get(v["proj"])
+    if pj is None:
+        raise ValueError("proj must be 2 or 3")
+    return out, pol, pj
+
+
+def variant_dict(proj="3d", **fields):
+    """A full variant dict: the library's default parameters (_lib.make_params) and run()'s sigma
+    schedule, overridden by `fields`."""
+    base = dict(w_path=100.5, w_slope=50.5, w_speed=0.5, w_obstacle=25.0, collision_threshold=0.99,
+                collision_penalty=100000.0, temperature=0.3, filter_k=3.5, filter_a=0.96, opt_filter_k=3.0,
+                opt_filter_a=0.92, sigma_base=RUN_POLICY["sigma_base"], sigma_div=RUN_POLICY["sigma_div"])
+    unknown = set(fields) - set(base)
+    if unknown:
+        raise ValueError(f"not fields of mppi_batch_variant: {sorted(unknown)}")
+    base.update(fields)
+    base["proj"] = proj
+    return base
+
+
 def normalise_heading(hv):
     """Row 0 of heading_sim widened to float64 and divided by sqrt((h0 h0 + h1 h1) + h2 h2) (the sum
     left to right, every operation rounded once), each component rounded to float32."""

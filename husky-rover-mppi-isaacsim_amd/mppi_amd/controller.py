@@ -476,7 +476,8 @@ class MPPI_Controller:
             self.loop += 1
         print("Number of loops:", self.loop)
 
-    def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None):
+    def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None,
+                  variants=None, episode_variant=None, score=None):
         """run() for many episodes at once on this controller's surface and parameters (mppi_batch_*,
         DESIGN.md §3.7): episode e starts at starts[e] = (x, y) with heading headings[e] (normalised
         as Robot does), wheels at rest and the controller's std_dev_u1 / std_dev_u2, and drives to
@@ -484,9 +485,19 @@ class MPPI_Controller:
 
         seeds: Philox key per episode (default the controller's seed + e); max_loops: the step cap
         (default the controller's); policy: dict(sigma_base, sigma_div, goal_tol[, check_every])
-        (default run()'s).  The robot and the controller's own loop state are not touched.  Returns
-        one dict per episode: x, y, z, lin_vel, ang_vel (the lists Robot accumulates: x, y, z begin
-        with the start pose and z = 0), loops, reached.
+        (default run()'s).  The robot and the controller's own loop state are not touched.
+
+        variants: the batch's variant table, a list of _lib.MppiBatchVariant or dicts
+        (_lib.make_variant's arguments: weights, collision_threshold / _penalty, temperature, the two
+        filters, sigma_base / sigma_div, proj); episode_variant[e]: the row episode e runs with
+        (-1 or None: the controller's parameters, `proj` and `policy`).  A weight sweep or the paired
+        2D / 3D runs of evaluate_trajectory.py are then one batch.  score: True (the controller's
+        weights) or a yardstick (variant or dict): every executed path is scored on the device with
+        that one cost function (mppi_batch_score).
+
+        Returns one dict per episode: x, y, z, lin_vel, ang_vel (the lists Robot accumulates: x, y, z
+        begin with the start pose and z = 0), loops, reached; with `score` the pair (that list,
+        dict(cost [E], terms [E, 4], collisions [E], rows [E])).
         """
         starts = np.asarray(starts, np.float64).reshape(-1, 2)
         E = starts.shape[0]
@@ -495,15 +506,22 @@ class MPPI_Controller:
         seeds = [self.seed + e for e in range(E)] if seeds is None else [int(s) for s in seeds]
         if len(seeds) != E:
             raise ValueError(f"{E} episodes but {len(seeds)} seeds")
+        ev = [-1] * E if episode_variant is None else [-1 if v is None else int(v) for v in episode_variant]
+        if len(ev) != E:
+            raise ValueError(f"{E} episodes but {len(ev)} variant indices")
+        if any(v >= 0 for v in ev) and not variants:
+            raise ValueError("episode_variant names rows of `variants`, which is empty")
         if self.engine is None:
             self.warp_setup()
         pol = _lib.make_policy(**(policy or {}))
         batch = _lib.Batch(self.engine, E)
         try:
+            if variants:
+                batch.set_variants(variants)
             for e in range(E):
                 batch.set_episode(e, _lib.make_state(starts[e, 0], starts[e, 1], headings[e], 0.0, 0.0,
                                                      goals[e, 0], goals[e, 1], self.std_dev_u1, self.std_dev_u2),
-                                  seeds[e])
+                                  seeds[e], ev[e])
             batch.run(self.max_loops if max_loops is None else int(max_loops), proj, pol)
             out = []
             for e in range(E):
@@ -512,7 +530,9 @@ class MPPI_Controller:
                 out.append(dict(x=[starts[e, 0]] + list(rows[:, 0]), y=[starts[e, 1]] + list(rows[:, 1]),
                                 z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
                                 loops=info["steps_last_run"], reached=info["reached"]))
-            return out
+            if score is None or score is False:
+                return out
+            return out, batch.score(None if score is True else score)
         finally:
             batch.close()
 

@@ -350,6 +350,51 @@ int  mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t
 int  mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows);
 int  mppi_batch_get_ms(mppi_batch* b, double* ms);  /* HIP-event time of the last run */
 
+/* ---- per-episode parameter variants ----
+ * The thesis's campaigns vary "weights in the cost function, various terrain constraints, various
+ * number of trajectories" (work summarise:52) and alternate a 2D and a 3D run of one task
+ * (evaluate_trajectory.py:80-126).  A variant is the set of parameters that one batch can vary per
+ * episode: plain kernel scalars that enter no plan, LDS size or shape.  Everything else
+ * (num_trajectories, num_iterations, dt, the control and velocity limits, wheel_offset,
+ * robot_radius, horizon, the scene, goal_tol, check_every) stays the context's and the run's. */
+typedef struct mppi_batch_variant {      /* 56 bytes */
+  float w_path, w_slope, w_speed, w_obstacle;       /* critics_warp.py:325-329 */
+  float collision_threshold, collision_penalty;     /* :251-253 */
+  float temperature;
+  float filter_k, filter_a, opt_filter_k, opt_filter_a;
+  float sigma_base, sigma_div;                      /* the loop policy's sigma schedule */
+  int32_t proj;                                     /* MPPI_PROJ_2D / MPPI_PROJ_3D */
+} mppi_batch_variant;
+/* out = the context's params with the given projection and the policy's sigma schedule: a variant
+ * that changes nothing against mppi_batch_run(b, proj, n, policy). */
+int  mppi_batch_variant_default(mppi_batch* b, int32_t proj, const mppi_loop_policy* policy,
+                                mppi_batch_variant* out);
+/* The batch's variant table: 0 <= n <= 1024 rows, copied to device memory; n = 0 clears it.  Each row
+ * passes the range checks of mppi_create (temperature > 0) and needs sigma_div != 0 and proj in
+ * {2, 3}; MPPI_EINVAL names the row and the field, and also answers a table shorter than an index an
+ * episode holds.  Synchronous, like every batch call. */
+int  mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant* v);
+/* Episode e runs with row `variant` of the table; -1 (the default of every episode) = the
+ * context's params and mppi_batch_run's proj / policy.  The index outlives mppi_batch_set_episode.
+ * For an episode that holds a variant mppi_batch_run's proj and policy->sigma_base / sigma_div are
+ * ignored; every step is bitwise the mppi_step of a context created with the batch context's
+ * params overridden by the variant, with the variant's projection, advanced by the rule above with
+ * the variant's sigma schedule.  Per step the rollout is launched once per projection in use. */
+int  mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant);
+/* Scores every episode's executed path with one common cost function, on the device
+ * (evaluate_trajectory.py:80-126 re-scores each logged run so).  The path of episode e is the log of
+ * its most recent run: rows 0 .. steps_last_run-1, waypoint = (x, y, z), lin_vel = v; no wheel
+ * arrays, so the slope critic runs on the body path, as mppi_score_paths with NULL wheels.
+ * yardstick: the weights, collision_threshold and collision_penalty every path is scored with (its
+ * other fields are not read); NULL = the context's params.  origins: NULL or [E] states of which x,
+ * y, goal_x, goal_y are read; NULL = the episode's position when its most recent run began and the
+ * episode's goal.  out: arrays of E (any may be NULL); rows [E] (may be NULL) receives each path's
+ * length.  An episode with no rows gets cost 0, terms 0, collisions 0.  The log stays on the
+ * device: 24 bytes per episode cross the bus.  mppi_get_score_ms of the batch's context reports the
+ * kernel's HIP-event time.  Synchronous; changes no state. */
+int  mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                      mppi_path_scores* out, int32_t* rows);
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

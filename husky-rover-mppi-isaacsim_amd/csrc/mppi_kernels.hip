@@ -1170,7 +1170,23 @@ __device__ __forceinline__ void lds_wait_ge(const int* f, int target, int& seen)
   seen = v;
 }
 
-template <int TB, int NC, bool DUMP, int DO = PAIR_D>
+// PIN: the step's uniform operands (cell_off, 1 / res, res, the wheel offset as pairs, dt) in
+// VGPRs, 9 in all.  In the separate-launch roles kernel the chain loop runs out of SGPRs: every
+// step it reloaded cell_off from the SGPR-spill lanes (2 v_readlane_b32 + a hazard s_nop) and
+// re-created the guard's compare constants (s_mov / s_movk: a VOP3 compare takes no literal).  A
+// packed op takes a VGPR pair as well as an SGPR pair, and the freed SGPRs hold the constants
+// across the loop.  Not in the server kernel (at its 112-VGPR limit, no reloads in its loop)
+// and not in the pair kernel (two workgroups per CU at 83 VGPRs, 4 spills, none in the loop).
+__device__ __forceinline__ f2 pin_vgpr(f2 x) {
+  asm("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ float pin_vgpr(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+template <int TB, int NC, bool DUMP, int DO = PAIR_D, bool PIN = false, bool RUN = true>
 __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& dem, const Traj& s, int tj,
                                               bool valid, int64_t kl, const float* ring_in, float* ring_out,
                                               const int* f_prod, int* f_chain, const int* const (&f_cons)[NC],
@@ -1199,7 +1215,15 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
       f2 posA = f2{s.x, s.y}, posB = posA;
       float4 nvA = make_float4(0.f, 0.f, 0.f, 0.f), nvB = nvA;
       float snA = 0.f, csA = 0.f, omA = 0.f, snB = 0.f, csB = 0.f, omB = 0.f;
-      const f2 cell_off = f2{-a.x_min, a.y_min};
+      f2 cell_off = f2{-a.x_min, a.y_min}, rinv2 = bc2(dem.rinv), res2 = bc2(dem.res), off2 = bc2(a.off);
+      float dt = a.dt;
+      if constexpr (PIN) {
+        cell_off = pin_vgpr(cell_off);
+        rinv2 = pin_vgpr(rinv2);
+        res2 = pin_vgpr(res2);
+        off2 = pin_vgpr(off2);
+        dt = pin_vgpr(dt);
+      }
       const float fi_hi = (float)(a.grid - 1), fj_lo = (float)(1 - a.rows);
       // entry (jj, ii) = (1 - tjj, ti + 1) of the table: element (ti + grid + 2) - tjj * (grid + 1) >= 0 from
       // dem.N, addressed as the uniform base plus a 32-bit byte offset (table < 4 GiB, check_grid):
@@ -1212,9 +1236,9 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
         f2 f;
         if constexpr (CD) {  // division by the verified reciprocal (cdiv_f), both axes at once
           const f2 aa = pos + cell_off;
-          const f2 q0 = aa * bc2(dem.rinv);
-          const f2 r = pk_fma(-q0, bc2(dem.res), aa);
-          f = pk_fma(r, bc2(dem.rinv), q0);
+          const f2 q0 = aa * rinv2;
+          const f2 r = pk_fma(-q0, res2, aa);
+          f = pk_fma(r, rinv2, q0);
         } else {
           f = f2{(pos.x - a.x_min) / a.res, (pos.y + a.y_min) / a.res};
         }
@@ -1223,9 +1247,7 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
         const int idx = __mul24(tjj, -nrow) + (ti + ncol0);
         nv = *reinterpret_cast<const float4*>(nbase + (uint32_t)(idx << 4));
       };
-      auto read_in = [&](int t, float& v, float& sn, float& cs, float& om, int need) __attribute__((always_inline)) {
-        if (need) lds_wait_ge(f_prod, need, seen_prod);
-        const float* ri = ring_in + (t % D) * RI * TB + tj;
+      auto read_in = [&](const float* ri, float& v, float& sn, float& cs, float& om) __attribute__((always_inline)) {
         v = ri[0];
         sn = ri[TB];
         cs = ri[2 * TB];
@@ -1233,38 +1255,46 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
       };
       {  // step 0's position and normal
         float v0;
-        read_in(0, v0, snA, csA, omA, 1);
+        lds_wait_ge(f_prod, 1, seen_prod);
+        read_in(ring_in + tj, v0, snA, csA, omA);
         Lean l;
         lean_init(l);
-        f2 p = advance_step<true>(hd, v0, a.dt, posA, l);
-        if (__builtin_expect(lean_bad(l), 0)) p = advance_step<false>(hd, v0, a.dt, posA, l);
+        f2 p = advance_step<true>(hd, v0, dt, posA, l);
+        if (__builtin_expect(lean_bad(l), 0)) p = advance_step<false>(hd, v0, dt, posA, l);
         posA = p;
         gather(posA, nvA);
       }
       // step t in set X (pos, normal in flight, sin / cos / 1 - cos); step t + 1 into set Y.
+      // rin: the ring_in slot of step t + 1, ro: the ring_out slot of step t (both with tj).
       // Even steps wait for two steps' worth of progress (the producer's steps t + 1, t + 2 and
-      // the consumers' ring slots of t, t + 1), odd steps are covered by them.
+      // the consumers' ring slots of t, t + 1), odd steps are covered by them.  (One run-ahead
+      // limit derived from the cached counters in place of the three target checks measured
+      // slower, checked at the step's start or in two parts: the rings are too shallow for the
+      // chain to run more than an iteration or two without a counter read, and the catch-up then
+      // costs more out of line than the checks do in line, profiles/chain_bookkeeping_notes.md.)
       // more = t + 1 < H as a compile-time tag: the loop body has no branch around the next
       // step's advance and gather, so the scheduler can interleave them with step t's outputs
-      auto it = [&](auto even_tag, auto more_tag, int t, f2& pX, float4& nX, float& snX, float& csX, float& omX,
-                    f2& pY, float4& nY, float& snY, float& csY, float& omY) __attribute__((always_inline)) {
-        constexpr bool EVEN = decltype(even_tag)::value;
+      auto it = [&](auto even_tag, auto more_tag, int t, const float* rin, float* ro, f2& pX, float4& nX, float& snX,
+                    float& csX, float& omX, f2& pY, float4& nY, float& snY, float& csY, float& omY)
+                    __attribute__((always_inline)) {
         constexpr bool more = decltype(more_tag)::value;
+        constexpr bool EVEN = decltype(even_tag)::value;
         float v1 = 0.f;
-        if constexpr (more) read_in(t + 1, v1, snY, csY, omY, EVEN ? min(t + 3, H) : 0);
+        if constexpr (more && EVEN) lds_wait_ge(f_prod, min(t + 3, H), seen_prod);
+        if constexpr (more) read_in(rin, v1, snY, csY, omY);
         const f2 nxy = f2{nX.x, nX.y};
         const float nz = nX.z;
         Lean l;
         lean_init(l);
         Head ho = orient_step<true>(nxy, nz, hd, snX, csX, omX, l);
         f2 p1 = pX;
-        if constexpr (more) p1 = advance_step<true, false>(ho, v1, a.dt, pX, l);
+        if constexpr (more) p1 = advance_step<true, false>(ho, v1, dt, pX, l);
         if (__builtin_expect(lean_bad(l), 0)) {  // operand outside the fast range: IEEE redo
           ho = orient_step<false>(nxy, nz, hd, snX, csX, omX, l);
-          if constexpr (more) p1 = advance_step<false>(ho, v1, a.dt, pX, l);
+          if constexpr (more) p1 = advance_step<false>(ho, v1, dt, pX, l);
         }
         // wheel offset right = 0.2 * cross(normal, current_hv) (projection_warp.py:333)
-        const f2 cxy = bc2(a.off) * cross_xy(nxy, nz, ho.xy, ho.z);
+        const f2 cxy = off2 * cross_xy(nxy, nz, ho.xy, ho.z);
         if constexpr (more) {
           pY = p1;
           gather(pY, nY);
@@ -1273,7 +1303,6 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
 #pragma unroll
           for (int c = 0; c < NC; ++c) lds_wait_ge(f_cons[c], t - DO + 2, seen_cons[c]);
         }
-        float* ro = ring_out + (t % DO) * 4 * TB + tj;
         ro[0] = pX.x;
         ro[TB] = pX.y;
         ro[2 * TB] = cxy.x;
@@ -1291,16 +1320,35 @@ __device__ __forceinline__ void chain_wave_3d(const RolloutArgs& a, const Dem& d
         lds_store_release(f_chain, t + 1);
         hd = ho;
       };
-      int t = 0;
-      for (; t + 2 < H; t += 2) {
-        it(T_{}, T_{}, t, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
-        it(F_{}, T_{}, t + 1, posB, nvB, snB, csB, omB, posA, nvA, snA, csA, omA);
+      // The running ring slot: so = (t % D) * SL for the even step t of an iteration, the same in
+      // both rings (equal depths and slot sizes).  Step t writes slot so, step t + 1 reads and
+      // writes so + SL (D even: never the wrap), step t + 2 reads the wrapped so + 2 SL, which
+      // is the next iteration's so.  No division by D per step.  RUN = false (the pair kernel)
+      // forms the slots from t as before: there the running slot measured 1-2 % slower (C4 shard,
+      // C5 rollout), fewer instructions or not (profiles/chain_bookkeeping_notes.md).
+      static_assert(D == DO && D % 2 == 0 && RI == 4, "one running slot serves both rings");
+      constexpr int SL = 4 * TB;
+      const float* const ri0 = ring_in + tj;
+      float* const ro0 = ring_out + tj;
+      const int last = H - 2;  // the loop runs the even steps with two steps after them
+      int t = 0, so = 0;
+      for (; RUN ? t < last : t + 2 < H; t += 2) {
+        int so2 = so + 2 * SL;
+        so2 = so2 == D * SL ? 0 : so2;
+        if constexpr (!RUN) {
+          so = (t % D) * SL;
+          so2 = ((t + 2) % D) * SL;
+        }
+        it(T_{}, T_{}, t, ri0 + so + SL, ro0 + so, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
+        it(F_{}, T_{}, t + 1, ri0 + so2, ro0 + so + SL, posB, nvB, snB, csB, omB, posA, nvA, snA, csA, omA);
+        so = so2;
       }
+      if constexpr (!RUN) so = (t % D) * SL;
       if (t + 1 < H) {  // the last two steps
-        it(T_{}, T_{}, t, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
-        it(F_{}, F_{}, t + 1, posB, nvB, snB, csB, omB, posA, nvA, snA, csA, omA);
+        it(T_{}, T_{}, t, ri0 + so + SL, ro0 + so, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
+        it(F_{}, F_{}, t + 1, ri0, ro0 + so + SL, posB, nvB, snB, csB, omB, posA, nvA, snA, csA, omA);
       } else {  // the last step (H odd)
-        it(T_{}, F_{}, t, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
+        it(T_{}, F_{}, t, ri0, ro0 + so, posA, nvA, snA, csA, omA, posB, nvB, snB, csB, omB);
       }
   };
   if (dem.cdiv)
@@ -1424,8 +1472,8 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
     if constexpr (PROJ == 3) {
       const int* cons[1] = {f_cons};
       int seen_c[1] = {0};
-      chain_wave_3d<TB, 1, DUMP>(a, dem, s, tj, valid, kl, ring_in, ring_out, f_prod, f_chain, cons, seen_prod,
-                                 seen_c);
+      chain_wave_3d<TB, 1, DUMP, PAIR_D, false, false>(a, dem, s, tj, valid, kl, ring_in, ring_out, f_prod, f_chain,
+                                                       cons, seen_prod, seen_c);
     } else
     for (int sc = 0; sc < H; ++sc) {  // 2D: the planar step (projection_warp.py:353-382)
       wait_ge(f_prod, sc + 1, seen_prod);
@@ -1755,8 +1803,8 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
     if constexpr (PROJ == 3) {
       const int* cons[2] = {f_wheel, f_cost};
       int seen_cons[2] = {0, 0};
-      chain_wave_3d<TB, 2, DUMP, DO>(a, dem, s, tj, valid, kl, ring_in, ring_out, f_prod, f_chain, cons, seen_prod,
-                                 seen_cons);
+      chain_wave_3d<TB, 2, DUMP, DO, !FUSED>(a, dem, s, tj, valid, kl, ring_in, ring_out, f_prod, f_chain, cons,
+                                             seen_prod, seen_cons);
     } else
     for (int sc = 0; sc < H; ++sc) {  // 2D (projection_warp.py:373-382): no normal, wheels zero
       wait_ge(f_prod, sc + 1, seen_prod);

@@ -31,6 +31,12 @@ def main():
     res = subprocess.run([sys.executable, os.path.join(HERE, "loopcount.py"), out, KERNEL], check=True,
                          capture_output=True, text=True).stdout
     head = next(m.group(1) for m in re.finditer(r"loop (\.LBB\S+) \[.*'pk': (\d+)", res) if int(m.group(2)) >= 100)
+    # the backward branch may target the latch, laid out before the header: take the loop it is in
+    for ln in kernel_lines(out, KERNEL):
+        m = re.match(re.escape(head) + r":.*in Loop: Header=(BB\S+) ", ln.strip())
+        if m:
+            head = ".L" + m.group(1)
+            break
     hot = subprocess.run([sys.executable, os.path.join(HERE, "hotloop.py"), out, KERNEL, head, "2"], check=True,
                          capture_output=True, text=True).stdout
     per = float(re.search(r"([\d.]+) per step", hot).group(1))

@@ -1,0 +1,486 @@
+// C-ABI implementation (include/mppi.h): batched closed-loop episodes (mppi_batch_*).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "mppi.h"
+#include "mppi_ctx.h"
+#include "mppi_score.h"
+
+using namespace mppi;
+using namespace mppi::capi;
+
+struct mppi_batch {
+  mppi_ctx* c = nullptr;
+  int E = 0, blocks = 0, H = 0;
+  std::vector<BatchEpisode> host;     // the table as last read from / written to the device
+  std::vector<unsigned char> is_set;  // mppi_batch_set_episode was called for the episode
+  DeviceBuf<BatchEpisode> ep;
+  DeviceBuf<float> eps;
+  DeviceBuf<float> unom;
+  DeviceBuf<double> nodes;
+  DeviceBuf<float> cost;
+  DeviceBuf<float> fin;
+  DeviceBuf<float> log;
+  int log_cap = 0;
+  PinnedBuf<int> active_count;
+  Event ev[2];
+  double last_ms = 0;
+  bool failed = false;  // a HIP error of the batch: further runs are refused
+  // per-episode parameter variants (mppi_batch_set_variants / _set_episode_variant)
+  std::vector<mppi_batch_variant> variants;  // the table as last set
+  std::vector<int> ep_var;                   // [E] each episode's row, -1: none
+  DeviceBuf<BatchVariant> d_var;             // [kBatchMaxVariants]
+  DeviceBuf<int> d_ep_var;                   // [E]
+  // [E] x, y, goal_x, goal_y of each episode when its most recent run began (mppi_batch_score)
+  std::vector<std::array<float, 4>> origin;
+};
+static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
+
+namespace {
+
+BatchVariant device_variant(const mppi_batch_variant& v) {
+  BatchVariant r;
+  r.w_path = v.w_path;
+  r.w_slope = v.w_slope;
+  r.w_speed = v.w_speed;
+  r.w_obs = v.w_obstacle;
+  r.thr = v.collision_threshold;
+  r.pen = v.collision_penalty;
+  r.T = v.temperature;
+  r.fk = v.filter_k;
+  r.fa = v.filter_a;
+  r.ok = v.opt_filter_k;
+  r.oa = v.opt_filter_a;
+  r.sigma_base = v.sigma_base;
+  r.sigma_div = v.sigma_div;
+  r.proj = v.proj;
+  return r;
+}
+
+int batch_episode(mppi_batch* b, int32_t e) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (e < 0 || e >= b->E) return fail(MPPI_EINVAL, "episode index out of range");
+  return MPPI_OK;
+}
+
+// The episode table device -> host (waits for the context stream).
+int batch_pull(mppi_batch* b) {
+  mppi_ctx* c = b->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(b->host.data(), b->ep, (size_t)b->E * sizeof(BatchEpisode), hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol) {
+  mppi_ctx* c = b->c;
+  const Plan pl = make_plan(c);
+  if (!pl.roles || pl.blocks != b->blocks)
+    return fail(MPPI_ESTATE, "batch: the context does not run the role-split rollout plan (MPPI_ROLES=0)");
+  int rc = batch_pull(b);
+  if (rc) return rc;
+  int active = 0;
+  // the projections in use: a set episode's variant's, or the run's where it holds none
+  bool any_var = false, use_proj[4] = {false, false, false, false};
+  for (int e = 0; e < b->E; ++e) {
+    BatchEpisode& r = b->host[e];
+    b->origin[e] = {r.x0, r.y0, r.gx, r.gy};
+    if (b->is_set[e]) {
+      const int vi = b->ep_var[e];
+      any_var = any_var || vi >= 0;
+      use_proj[vi >= 0 ? b->variants[vi].proj : proj] = true;
+    }
+    r.steps_run = 0;
+    const bool outside = std::fabs(r.x0 - r.gx) > pol.goal_tol || std::fabs(r.y0 - r.gy) > pol.goal_tol;
+    r.active = b->is_set[e] && outside ? 1 : 0;
+    if (b->is_set[e] && !outside) r.reached = 1;
+    active += r.active;
+  }
+  b->last_ms = 0;
+  if (n_steps == 0 || active == 0) {
+    HIP_TRY(hipMemcpyAsync(b->ep, b->host.data(), (size_t)b->E * sizeof(BatchEpisode), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPPI_OK;
+  }
+  const size_t log_need = (size_t)b->E * n_steps * 8 * sizeof(float);
+  rc = grow(b->log, log_need, c->stream);
+  if (rc) return rc;
+  b->log_cap = n_steps;
+  HIP_TRY(hipMemcpyAsync(b->ep, b->host.data(), (size_t)b->E * sizeof(BatchEpisode), hipMemcpyHostToDevice,
+                         c->stream));
+  __atomic_store_n(b->active_count.get(), active, __ATOMIC_RELEASE);
+
+  RolloutArgs a;
+  FinishArgs f;
+  const mppi_state none{};
+  fill_rollout(c, pl, none, 0, nullptr, a);  // scene and parameters; the kernel patches the episode's part
+  a.clk = nullptr;
+  a.rec_m = nullptr;
+  a.ustore = nullptr;
+  a.inj_u1 = a.inj_u2 = nullptr;
+  a.k_offset = c->p.k_offset;
+  fill_finish(c, pl, none, f);
+  f.mode = 2;
+  BatchArgs z{};
+  z.var = any_var ? b->d_var : nullptr;  // null: the kernels of the batch without variants
+  z.ep_var = b->d_ep_var;
+  z.proj = proj;
+  z.ep = b->ep;
+  z.E = b->E;
+  z.blocks = b->blocks;
+  z.H = b->H;
+  z.k_pad = (int64_t)b->blocks * 256;
+  z.eps = b->eps;
+  z.unom = b->unom;
+  z.nodes = b->nodes;
+  z.cost = b->cost;
+  z.fin = b->fin;
+  z.log = b->log;
+  z.log_cap = b->log_cap;
+  z.sigma_base = pol.sigma_base;
+  z.sigma_div = pol.sigma_div;
+  z.goal_tol = pol.goal_tol;
+  z.horizon = c->p.horizon;
+  z.rwheel = c->p.robot_radius;
+  z.active_count = b->active_count;
+  const int every = pol.check_every > 0 ? pol.check_every : 16;
+  HIP_TRY(hipEventRecord(b->ev[0], c->stream));
+  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
+    const int m = std::min(every, n_steps - done);
+    for (int i = 0; i < m; ++i) {
+      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+      // one rollout launch per projection in use (a workgroup of the other projection's episode
+      // returns at once); without variants that is the run's projection alone
+      for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
+        if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
+      HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    done += m;
+  }
+  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
+  HIP_TRY(hipEventSynchronize(b->ev[1]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+  b->last_ms = ms;
+  return MPPI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mppi_batch_create(mppi_ctx* c, int32_t episodes, mppi_batch** out) {
+  if (!out) return fail(MPPI_EINVAL, "null argument");
+  *out = nullptr;
+  if (episodes < 1 || episodes > 4096) return fail(MPPI_EINVAL, "episodes must be in [1, 4096]");
+  if (!c) return fail(MPPI_EINVAL, "null context");
+  const int64_t K = c->p.num_trajectories;
+  const int64_t blocks = (K + PAIR_TRAJ - 1) / PAIR_TRAJ;
+  if (blocks < 1 || blocks > kBatchMaxRecords)
+    return fail(MPPI_EINVAL, "batch: num_trajectories must be in [1, 4096] (1 to 16 leaf records)");
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  std::unique_ptr<mppi_batch> b(new mppi_batch());
+  b->c = c;
+  b->E = episodes;
+  b->blocks = (int)blocks;
+  const int H = b->H = H_of(c);
+  const size_t E = (size_t)episodes;
+  b->host.assign(E, BatchEpisode{});
+  b->is_set.assign(E, 0);
+  b->ep_var.assign(E, -1);
+  b->origin.assign(E, std::array<float, 4>{0.0f, 0.0f, 0.0f, 0.0f});
+  if (b->ep.alloc(E * sizeof(BatchEpisode)) || b->d_var.alloc(kBatchMaxVariants * sizeof(BatchVariant)) ||
+      b->d_ep_var.alloc(E * sizeof(int)) ||
+      hipMemset(b->d_var, 0, kBatchMaxVariants * sizeof(BatchVariant)) != hipSuccess ||
+      hipMemset(b->d_ep_var, 0xff, E * sizeof(int)) != hipSuccess ||
+      b->eps.alloc(E * blocks * 2 * H * 256 * sizeof(float)) || b->unom.alloc(E * 4 * H * sizeof(float)) ||
+      b->nodes.alloc(E * blocks * (2 * H + 2) * sizeof(double)) || b->cost.alloc(E * blocks * 256 * sizeof(float)) ||
+      b->fin.alloc(E * (7 * H + 12) * sizeof(float)) || b->active_count.alloc(64) || b->ev[0].create() ||
+      b->ev[1].create() ||
+      hipMemset(b->ep, 0, E * sizeof(BatchEpisode)) != hipSuccess ||
+      hipMemset(b->unom, 0, E * 4 * H * sizeof(float)) != hipSuccess ||
+      hipMemset(b->cost, 0, E * blocks * 256 * sizeof(float)) != hipSuccess ||
+      hipMemset(b->fin, 0, E * (7 * H + 12) * sizeof(float)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {
+    const std::string why = hipGetErrorString(hipGetLastError());
+    return fail(MPPI_EHIP, "batch allocation failed: " + why);
+  }
+  *b->active_count = 0;
+  *out = b.release();
+  return MPPI_OK;
+}
+
+void mppi_batch_destroy(mppi_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->c->device);
+  if (b->c->stream) hipStreamSynchronize(b->c->stream);
+  delete b;
+}
+
+int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, uint64_t seed) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (!start) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  ServerCmd d;
+  state_fields(c->p, *start, d);
+  BatchEpisode r{};
+  r.x0 = d.x0;
+  r.y0 = d.y0;
+  r.h0x = d.h0x;
+  r.h0y = d.h0y;
+  r.h0z = d.h0z;
+  r.wl = d.wl;
+  r.wr = d.wr;
+  r.gx = d.gx;
+  r.gy = d.gy;
+  r.s1 = d.s1;
+  r.s2 = d.s2;
+  r.pf_far = d.pf_far;
+  r.speed_on = d.speed_on;
+  r.igx = d.igx;
+  r.igy = d.igy;
+  r.pf_scale = d.pf_scale;
+  r.seed = seed;
+  b->host[e] = r;
+  b->is_set[e] = 1;
+  HIP_TRY(hipMemcpyAsync(b->ep + e, &b->host[e], sizeof(BatchEpisode), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->unom + (size_t)e * 4 * b->H, 0, (size_t)4 * b->H * sizeof(float), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop_policy* policy) {
+  if (!b || !policy) return fail(MPPI_EINVAL, "null argument");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  if (n_steps < 0) return fail(MPPI_EINVAL, "n_steps must be >= 0");
+  if (policy->check_every < 0) return fail(MPPI_EINVAL, "check_every must be >= 0");
+  if (!(policy->sigma_div != 0.0f)) return fail(MPPI_EINVAL, "sigma_div must be non-zero");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
+  if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = batch_run(b, proj, n_steps, *policy);
+  if (rc == MPPI_EHIP) b->failed = true;
+  return rc;
+}
+
+int mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total,
+                           int32_t* steps_last_run, int32_t* reached, float* u1, float* u2) {
+  if (int rc = batch_episode(b, e)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  BatchEpisode& r = b->host[e];
+  const int H = b->H;
+  HIP_TRY(hipMemcpyAsync(&r, b->ep + e, sizeof(BatchEpisode), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const float* unom = b->unom + ((size_t)e * 2 + r.cur) * 2 * H;
+  if (u1) HIP_TRY(hipMemcpyAsync(u1, unom, H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (u2) HIP_TRY(hipMemcpyAsync(u2, unom + H, H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (u1 || u2) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (state) {
+    state->x = r.x0;
+    state->y = r.y0;
+    state->heading[0] = r.h0x;
+    state->heading[1] = r.h0y;
+    state->heading[2] = r.h0z;
+    state->left_wheel_speed = r.wl;
+    state->right_wheel_speed = r.wr;
+    state->goal_x = r.gx;
+    state->goal_y = r.gy;
+    state->std_dev_u1 = r.s1;
+    state->std_dev_u2 = r.s2;
+  }
+  if (steps_total) *steps_total = (int64_t)r.step;
+  if (steps_last_run) *steps_last_run = r.steps_run;
+  if (reached) *reached = r.reached;
+  return MPPI_OK;
+}
+
+int mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "log range out of bounds");
+  if (count > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  BatchEpisode& r = b->host[e];
+  HIP_TRY(hipMemcpyAsync(&r, b->ep + e, sizeof(BatchEpisode), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((int64_t)first + count > r.steps_run) return fail(MPPI_EINVAL, "log range beyond the steps of the last run");
+  if (count == 0) return MPPI_OK;
+  HIP_TRY(hipMemcpyAsync(rows, b->log + ((size_t)e * b->log_cap + first) * 8, (size_t)count * 8 * sizeof(float),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_get_ms(mppi_batch* b, double* ms) {
+  if (!b || !ms) return fail(MPPI_EINVAL, "null argument");
+  *ms = b->last_ms;
+  return MPPI_OK;
+}
+
+int mppi_batch_variant_default(mppi_batch* b, int32_t proj, const mppi_loop_policy* policy,
+                               mppi_batch_variant* out) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!policy || !out) return fail(MPPI_EINVAL, "null argument");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  const mppi_params& p = b->c->p;
+  out->w_path = p.w_path;
+  out->w_slope = p.w_slope;
+  out->w_speed = p.w_speed;
+  out->w_obstacle = p.w_obstacle;
+  out->collision_threshold = p.collision_threshold;
+  out->collision_penalty = p.collision_penalty;
+  out->temperature = p.temperature;
+  out->filter_k = p.filter_k;
+  out->filter_a = p.filter_a;
+  out->opt_filter_k = p.opt_filter_k;
+  out->opt_filter_a = p.opt_filter_a;
+  out->sigma_base = policy->sigma_base;
+  out->sigma_div = policy->sigma_div;
+  out->proj = proj;
+  return MPPI_OK;
+}
+
+int mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant* v) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (n < 0 || n > kBatchMaxVariants) return fail(MPPI_EINVAL, "variants: n must be in [0, 1024]");
+  if (n > 0 && !v) return fail(MPPI_EINVAL, "null argument");
+  for (int i = 0; i < n; ++i) {
+    const std::string row = "variant row " + std::to_string(i) + ": ";
+    // the checks of mppi_create on the fields a variant overrides, and the run's on sigma_div / proj
+    if (!(v[i].temperature > 0.0f)) return fail(MPPI_EINVAL, row + "temperature must be > 0");
+    if (!(v[i].sigma_div != 0.0f)) return fail(MPPI_EINVAL, row + "sigma_div must be non-zero");
+    if (v[i].proj != MPPI_PROJ_2D && v[i].proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, row + "proj must be 2 or 3");
+  }
+  for (int e = 0; e < b->E; ++e)
+    if (b->ep_var[e] >= n)
+      return fail(MPPI_EINVAL, "variants: episode " + std::to_string(e) + " holds row " +
+                                   std::to_string(b->ep_var[e]) + " of the table, n = " + std::to_string(n));
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<BatchVariant> rows((size_t)n);
+  for (int i = 0; i < n; ++i) rows[i] = device_variant(v[i]);
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(b->d_var, rows.data(), (size_t)n * sizeof(BatchVariant), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // rows is pageable and dies here
+  }
+  b->variants.assign(v, v + n);
+  return MPPI_OK;
+}
+
+int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (variant < -1 || variant >= (int32_t)b->variants.size())
+    return fail(MPPI_EINVAL, "variant index " + std::to_string(variant) + " outside the table of " +
+                                 std::to_string(b->variants.size()) + " rows");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  b->ep_var[e] = variant;
+  HIP_TRY(hipMemcpyAsync(b->d_ep_var + e, &b->ep_var[e], sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                     mppi_path_scores* out, int32_t* rows) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!out) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score: no costmap: call mppi_set_costmap first");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t E = (size_t)b->E;
+  if (!b->log) {  // no run yet: no episode has a row
+    if (out->cost) std::memset(out->cost, 0, E * 4);
+    if (out->terms) std::memset(out->terms, 0, E * 16);
+    if (out->collisions) std::memset(out->collisions, 0, E * 4);
+    if (rows) std::memset(rows, 0, E * 4);
+    return MPPI_OK;
+  }
+  const mppi_params& p = c->p;
+  std::vector<ScoreGoal> goals(E);
+  for (size_t e = 0; e < E; ++e) {
+    mppi_state st{};
+    if (origins) {
+      st.x = origins[e].x;
+      st.y = origins[e].y;
+      st.goal_x = origins[e].goal_x;
+      st.goal_y = origins[e].goal_y;
+    } else {
+      st.x = b->origin[e][0];
+      st.y = b->origin[e][1];
+      st.goal_x = b->origin[e][2];
+      st.goal_y = b->origin[e][3];
+    }
+    ServerCmd d;
+    state_fields(p, st, d);
+    goals[e] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
+  }
+  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows]
+  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16;
+  DeviceBuf<char> dbuf;
+  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt));
+  char* buf = dbuf;
+  ScoreGoal* d_goals = (ScoreGoal*)buf;
+  float* d_cost = (float*)(buf + bg);
+  float* d_terms = (float*)(buf + bg + bn);
+  int32_t* d_col = (int32_t*)(buf + bg + bn + bt);
+  int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
+  ScoreArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.log = b->log;
+  a.goals = d_goals;
+  a.lengths = &b->ep->steps_run;  // the episode table's own counters, one record apart
+  a.len_step = (int)(sizeof(BatchEpisode) / sizeof(int32_t));
+  a.rows_out = d_rows;
+  a.n = (int64_t)E;
+  a.stride = b->log_cap;
+  a.cm = c->cmap.cm;
+  a.cm_size = c->cmap.size;
+  a.hw = c->cmap.hw;
+  a.res_c = c->cmap.res;
+  a.vmax = p.v_max_linear;
+  a.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+  a.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+  a.w_path = yardstick ? yardstick->w_path : p.w_path;
+  a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+  a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+  a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  a.cost = d_cost;
+  a.terms = d_terms;
+  a.collisions = d_col;
+  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
+  int rc = MPPI_OK;
+  if (e == hipSuccess) rc = run_score(c, a);
+  if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, E * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && rows) e = hipMemcpyAsync(rows, d_rows, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("batch_score: ") + hipGetErrorString(e));
+  return MPPI_OK;
+}
+
+}  // extern "C"

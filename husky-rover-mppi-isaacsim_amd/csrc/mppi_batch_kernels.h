@@ -20,7 +20,9 @@ __global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b
   const int H = b.H, NB = (H + 1) >> 1;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   float* eps = b.eps + (size_t)e * b.blocks * 2 * H * 256;
-  noise_waves(ep->seed, ep->step * (uint64_t)NB, k_offset, H, (int)blockIdx.x * 4 + wave, b.blocks * NB * 4,
+  // the leaf blocks the episode runs: no normals for the others (the layout keeps the batch's stride)
+  const int blocks = b.scene ? b.scene->rec[e].blocks : b.blocks;
+  noise_waves(ep->seed, ep->step * (uint64_t)NB, k_offset, H, (int)blockIdx.x * 4 + wave, blocks * NB * 4,
               (int)gridDim.x * 4, eps, (int)threadIdx.x & 63);
 }
 
@@ -29,14 +31,28 @@ __global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b
 // buffer slices patched in, and, for an episode that holds a variant, its row of the table
 // (BatchArgs::var) over the parameters a variant may override.  With a table the launch serves the
 // episodes of projection PROJ only (the row's, or the run's for an episode without a variant): a
-// workgroup of another projection's episode returns at once, like an inactive one.
+// workgroup of another projection's episode returns at once, like an inactive one.  With a scene
+// table (BatchArgs::scene) the episode's K and, where it holds slots, its DEM, normal table and
+// costmap replace the launch's; the grid is the context's, and a leaf block past the episode's
+// ceil(K / 256) returns first of all.
 template <int PROJ>
 __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const RolloutArgs a_in, const BatchArgs b) {
   const int e = blockIdx.y;
+  // (null: no episode holds a scene slot or a K of its own) a leaf block beyond the episode's K
+  if (b.scene && (int)blockIdx.x >= b.scene->rec[e].blocks) return;
   const BatchEpisode* ep = b.ep + e;
   if (!ep->active) return;
   RolloutArgs a = a_in;
   const int H = a.H;
+  if (b.scene) {  // patched into the copy: roles_body reads K as kl < a.K only, the scene through a
+    const BatchScene s = b.scene->rec[e];
+    a.K = s.K;
+    if (s.dem >= 0) {
+      a.Z = b.scene->dem_z[s.dem];
+      a.ntab = b.scene->dem_ntab[s.dem];
+    }
+    if (s.cm >= 0) a.cm = b.scene->cms[s.cm];
+  }
   if (b.var) {  // (null: no episode holds a variant, and the launch is the run's projection)
     const int vi = b.ep_var[e];
     if (vi >= 0) {
@@ -108,6 +124,15 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
       sigma_div = v->sigma_div;
     }
   }
+  int n = b.blocks;  // the episode's leaf records
+  if (b.scene) {
+    const BatchScene s = b.scene->rec[e];
+    n = s.blocks;
+    if (s.dem >= 0) {  // row 0 of the optimal rollout reads the DEM
+      f.Z = b.scene->dem_z[s.dem];
+      f.ntab = b.scene->dem_ntab[s.dem];
+    }
+  }
   const int cur_buf = ep->cur;
   const float gx = ep->gx, gy = ep->gy;
   const int row = ep->steps_run;
@@ -127,7 +152,6 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   double* lnode = reinterpret_cast<double*>(smem_raw);
   PairScale* lps = reinterpret_cast<PairScale*>(smem_raw + (size_t)E * sizeof(double));
   const double* recs = b.nodes + (size_t)e * b.blocks * E;
-  const int n = b.blocks;
   if (n > 1) {
     float* lm = reinterpret_cast<float*>(lps + 15);
     if (tid < 16) lm[tid] = (tid < n) ? (float)recs[(size_t)tid * E] : INFINITY;

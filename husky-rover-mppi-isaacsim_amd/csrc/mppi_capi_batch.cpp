@@ -4,12 +4,14 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "mppi.h"
+#include "mppi_batch_scene.h"
 #include "mppi_ctx.h"
 #include "mppi_score.h"
 
@@ -40,8 +42,15 @@ struct mppi_batch {
   DeviceBuf<int> d_ep_var;                   // [E]
   // [E] x, y, goal_x, goal_y of each episode when its most recent run began (mppi_batch_score)
   std::vector<std::array<float, 4>> origin;
+  // per-episode scenes and trajectory counts (mppi_batch_set_dem / _set_costmap / _set_episode_scene /
+  // _set_episode_trajectories): `book` decides, the rest is the slots' memory and the kernels' tables
+  BatchSceneBook book;
+  std::vector<Dem> dems;              // [kBatchMaxDems] a live slot owns its heights and normal table
+  std::vector<DeviceBuf<float>> cms;  // [kBatchMaxCostmaps]
+  DeviceBuf<BatchSceneTable> d_tab;   // the slots' pointer tables and the [E] records (BatchArgs::scene)
 };
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
+static_assert(sizeof(SceneRecord) == sizeof(BatchScene), "SceneRecord is BatchScene field for field");
 
 namespace {
 
@@ -67,6 +76,91 @@ BatchVariant device_variant(const mppi_batch_variant& v) {
 int batch_episode(mppi_batch* b, int32_t e) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
   if (e < 0 || e >= b->E) return fail(MPPI_EINVAL, "episode index out of range");
+  return MPPI_OK;
+}
+
+SceneGeom dem_geom(const mppi_ctx* c) {
+  return SceneGeom{c->dem.rows, c->dem.cols, c->dem.x_min, c->dem.y_min, c->dem.res};
+}
+SceneGeom costmap_geom(const mppi_ctx* c) { return SceneGeom{c->cmap.size, 0, c->cmap.hw, c->cmap.res, 0.0f}; }
+
+// Episode e's scene record host -> device (synchronous), unless it still equals `before`.
+int push_scene(mppi_batch* b, int e, const SceneRecord& before) {
+  const SceneRecord r = b->book.record(e);
+  if (std::memcmp(&r, &before, sizeof(r)) == 0) return MPPI_OK;
+  HIP_TRY(hipMemcpyAsync(b->d_tab->rec + e, &r, sizeof(r), hipMemcpyHostToDevice, b->c->stream));
+  HIP_TRY(hipStreamSynchronize(b->c->stream));
+  return MPPI_OK;
+}
+
+// Every slot an episode in use holds still has the context's geometry (the launch's rinv_res, cdiv
+// and plan are the context's): not after a mppi_set_dem / mppi_set_costmap of another size in between.
+int scene_geometry(const mppi_batch* b) {
+  int s = b->book.mismatch(kSceneDem, dem_geom(b->c));
+  if (s >= 0)
+    return fail(MPPI_ESTATE, "batch: DEM slot " + std::to_string(s) +
+                                 " was set with another geometry than the context's current DEM");
+  s = b->book.mismatch(kSceneCostmap, costmap_geom(b->c));
+  if (s >= 0)
+    return fail(MPPI_ESTATE, "batch: costmap slot " + std::to_string(s) +
+                                 " was set with another geometry than the context's current costmap");
+  return MPPI_OK;
+}
+
+int slot_index(const mppi_batch* b, SceneKind k, int32_t slot) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!b->book.in_range(k, slot))
+    return fail(MPPI_EINVAL, std::string(k == kSceneDem ? "DEM" : "costmap") + " slot " + std::to_string(slot) +
+                                 " outside [0, " + std::to_string(b->book.slots(k)) + ")");
+  return MPPI_OK;
+}
+
+// Free the slot unless an episode holds it.  (Its entry of the device table goes stale: no record names it.)
+int slot_free(mppi_batch* b, SceneKind k, int32_t slot) {
+  int who = -1;
+  if (b->book.free_slot(k, slot, &who) == kSceneSlotHeld)
+    return fail(MPPI_EINVAL, std::string(k == kSceneDem ? "DEM" : "costmap") + " slot " + std::to_string(slot) +
+                                 " is held by episode " + std::to_string(who));
+  if (k == kSceneDem)
+    b->dems[slot] = Dem{};
+  else
+    b->cms[slot].reset();
+  return MPPI_OK;
+}
+
+// A buffer of `bytes` for a slot: `cur` when it is large enough, else a new one in `fresh` (`cur`
+// stays as it is until the caller moves `fresh` in).  A failure leaves the batch usable.
+template <class T>
+int slot_alloc(const DeviceBuf<T>& cur, DeviceBuf<T>& fresh, size_t bytes, const char* what, int32_t slot) {
+  if (cur && bytes <= cur.cap()) return MPPI_OK;
+  if (fresh.alloc(bytes)) {
+    (void)hipGetLastError();
+    return fail(MPPI_EHIP, std::string(what) + " slot " + std::to_string(slot) + ": allocation of " +
+                               std::to_string(bytes) + " bytes failed");
+  }
+  return MPPI_OK;
+}
+
+// The costmap slot's buffer for the context costmap's size (`fresh` holds a new one until the caller
+// has filled it), or the error.
+int costmap_slot_buffer(mppi_batch* b, int32_t slot, const char* who, DeviceBuf<float>& fresh, float** dst) {
+  mppi_ctx* c = b->c;
+  if (!c->cmap.cm || c->cmap.size <= 0)
+    return fail(MPPI_ESTATE, std::string(who) + ": no costmap: call mppi_set_costmap first (a slot takes the context's geometry)");
+  const size_t bytes = (size_t)c->cmap.size * c->cmap.size * sizeof(float);
+  if (int rc = slot_alloc(b->cms[slot], fresh, bytes, "costmap", slot)) return rc;
+  *dst = fresh ? fresh.get() : b->cms[slot].get();
+  return MPPI_OK;
+}
+
+// The filled buffer becomes the slot's contents (synchronous).
+int costmap_slot_publish(mppi_batch* b, int32_t slot, DeviceBuf<float>& fresh) {
+  mppi_ctx* c = b->c;
+  if (fresh) b->cms[slot] = std::move(fresh);
+  const float* p = b->cms[slot];
+  HIP_TRY(hipMemcpyAsync(b->d_tab->cms + slot, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  b->book.set_slot(kSceneCostmap, slot, costmap_geom(c));
   return MPPI_OK;
 }
 
@@ -152,6 +246,7 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   z.horizon = c->p.horizon;
   z.rwheel = c->p.robot_radius;
   z.active_count = b->active_count;
+  z.scene = b->book.need_table() ? b->d_tab.get() : nullptr;  // null: the kernels of the batch without scenes
   const int every = pol.check_every > 0 ? pol.check_every : 16;
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
   for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
@@ -200,8 +295,16 @@ int mppi_batch_create(mppi_ctx* c, int32_t episodes, mppi_batch** out) {
   b->is_set.assign(E, 0);
   b->ep_var.assign(E, -1);
   b->origin.assign(E, std::array<float, 4>{0.0f, 0.0f, 0.0f, 0.0f});
+  b->book = BatchSceneBook(episodes, kBatchMaxDems, kBatchMaxCostmaps, K);
+  b->dems.resize(kBatchMaxDems);
+  b->cms.resize(kBatchMaxCostmaps);
+  std::vector<SceneRecord> recs(E);
+  for (size_t e = 0; e < E; ++e) recs[e] = b->book.record((int)e);
+  const size_t tab_bytes = offsetof(BatchSceneTable, rec) + E * sizeof(BatchScene);
   if (b->ep.alloc(E * sizeof(BatchEpisode)) || b->d_var.alloc(kBatchMaxVariants * sizeof(BatchVariant)) ||
-      b->d_ep_var.alloc(E * sizeof(int)) ||
+      b->d_ep_var.alloc(E * sizeof(int)) || b->d_tab.alloc(tab_bytes) ||
+      hipMemset(b->d_tab, 0, tab_bytes) != hipSuccess ||
+      hipMemcpy(b->d_tab->rec, recs.data(), E * sizeof(BatchScene), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(b->d_var, 0, kBatchMaxVariants * sizeof(BatchVariant)) != hipSuccess ||
       hipMemset(b->d_ep_var, 0xff, E * sizeof(int)) != hipSuccess ||
       b->eps.alloc(E * blocks * 2 * H * 256 * sizeof(float)) || b->unom.alloc(E * 4 * H * sizeof(float)) ||
@@ -256,6 +359,7 @@ int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, ui
   r.seed = seed;
   b->host[e] = r;
   b->is_set[e] = 1;
+  b->book.mark_set(e);
   HIP_TRY(hipMemcpyAsync(b->ep + e, &b->host[e], sizeof(BatchEpisode), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->unom + (size_t)e * 4 * b->H, 0, (size_t)4 * b->H * sizeof(float), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -273,6 +377,7 @@ int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
+  if (int rc_g = scene_geometry(b)) return rc_g;
   HIP_TRY(hipSetDevice(c->device));
   const int rc = batch_run(b, proj, n_steps, *policy);
   if (rc == MPPI_EHIP) b->failed = true;
@@ -401,6 +506,106 @@ int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
   return MPPI_OK;
 }
 
+int mppi_batch_set_dem(mppi_batch* b, int32_t slot, const float* z_host) {
+  if (int rc = slot_index(b, kSceneDem, slot)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!z_host) return slot_free(b, kSceneDem, slot);
+  if (!c->dem.Z || c->dem.rows <= 0)
+    return fail(MPPI_ESTATE, "batch_set_dem: no DEM: call mppi_set_dem first (a slot takes the context's geometry)");
+  const int rows = c->dem.rows, cols = c->dem.cols;
+  const size_t zb = (size_t)rows * cols * sizeof(float);
+  const size_t nb = ((size_t)rows + 1) * ((size_t)cols + 1) * sizeof(float4);
+  Dem& d = b->dems[slot];
+  DeviceBuf<float> nz;
+  DeviceBuf<float4> nt;
+  if (int rc = slot_alloc(d.Z, nz, zb, "DEM", slot)) return rc;
+  if (int rc = slot_alloc(d.ntab, nt, nb, "DEM", slot)) return rc;
+  if (nz) d.Z = std::move(nz);
+  if (nt) d.ntab = std::move(nt);
+  d.rows = rows;
+  d.cols = cols;
+  d.x_min = c->dem.x_min;
+  d.y_min = c->dem.y_min;
+  d.res = c->dem.res;
+  d.rinv_res = c->dem.rinv_res;
+  const float* zp = d.Z;
+  const float4* np = d.ntab;
+  HIP_TRY(hipMemcpyAsync(d.Z, z_host, zb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_normal_table(d.Z, rows, cols, d.res, d.ntab, c->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_tab->dem_z + slot, &zp, sizeof(zp), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_tab->dem_ntab + slot, &np, sizeof(np), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  b->book.set_slot(kSceneDem, slot, dem_geom(c));
+  return MPPI_OK;
+}
+
+int mppi_batch_set_costmap(mppi_batch* b, int32_t slot, const float* cm_host) {
+  if (int rc = slot_index(b, kSceneCostmap, slot)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!cm_host) return slot_free(b, kSceneCostmap, slot);
+  DeviceBuf<float> fresh;
+  float* dst = nullptr;
+  if (int rc = costmap_slot_buffer(b, slot, "batch_set_costmap", fresh, &dst)) return rc;
+  HIP_TRY(hipMemcpyAsync(dst, cm_host, (size_t)c->cmap.size * c->cmap.size * sizeof(float), hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return costmap_slot_publish(b, slot, fresh);
+}
+
+int mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacles, int32_t n, double origin_x,
+                             double origin_y, double r_robot, int32_t power, int32_t metric, float* out_host) {
+  if (int rc = slot_index(b, kSceneCostmap, slot)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  // the builder's own resolution (mppi_build_costmap) must be the one the kernels index the slots with
+  const double hw = (double)c->cmap.hw;
+  if (c->cmap.size > 0 && (float)(2 * hw / c->cmap.size) != c->cmap.res)
+    return fail(MPPI_EINVAL, "batch_build_costmap: the context costmap's resolution is not 2 * half_width / size");
+  DeviceBuf<float> fresh;
+  float* dst = nullptr;
+  if (int rc = costmap_slot_buffer(b, slot, "batch_build_costmap", fresh, &dst)) return rc;
+  if (int rc = build_costmap_into(c, obstacles, n, c->cmap.size, hw, origin_x, origin_y, r_robot, power, metric, dst,
+                                  out_host))
+    return rc;
+  return costmap_slot_publish(b, slot, fresh);
+}
+
+int mppi_batch_set_episode_scene(mppi_batch* b, int32_t e, int32_t dem_slot, int32_t costmap_slot) {
+  if (int rc = batch_episode(b, e)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  SceneKind bad = kSceneDem;
+  const SceneRecord before = b->book.record(e);
+  const SceneError err = b->book.set_episode_scene(e, dem_slot, costmap_slot, &bad);
+  if (err != kSceneOk) {
+    const int32_t s = bad == kSceneDem ? dem_slot : costmap_slot;
+    const std::string what = std::string(bad == kSceneDem ? "DEM" : "costmap") + " slot " + std::to_string(s);
+    if (err == kSceneSlotRange)
+      return fail(MPPI_EINVAL, "episode " + std::to_string(e) + ": " + what + " outside [-1, " +
+                                   std::to_string(b->book.slots(bad)) + ")");
+    return fail(MPPI_EINVAL, "episode " + std::to_string(e) + ": " + what + " is empty");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  return push_scene(b, e, before);
+}
+
+int mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_trajectories) {
+  if (int rc = batch_episode(b, e)) return rc;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  const SceneRecord before = b->book.record(e);
+  if (b->book.set_episode_K(e, num_trajectories) != kSceneOk)
+    return fail(MPPI_EINVAL, "episode " + std::to_string(e) + ": num_trajectories " + std::to_string(num_trajectories) +
+                                 " outside [1, " + std::to_string(c->p.num_trajectories) + "] (0: the context's)");
+  HIP_TRY(hipSetDevice(c->device));
+  return push_scene(b, e, before);
+}
+
 int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
                      mppi_path_scores* out, int32_t* rows) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
@@ -409,6 +614,7 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score: no costmap: call mppi_set_costmap first");
+  if (int rc_g = scene_geometry(b)) return rc_g;
   HIP_TRY(hipSetDevice(c->device));
   const size_t E = (size_t)b->E;
   if (!b->log) {  // no run yet: no episode has a row
@@ -437,16 +643,27 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
     state_fields(p, st, d);
     goals[e] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
   }
-  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows]
-  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16;
+  // each path on its episode's costmap: the slot's where the episode holds one, else the context's
+  // (no array at all while no episode in use holds a costmap slot)
+  std::vector<const float*> cmaps;
+  if (b->book.any_costmap_held()) {
+    cmaps.resize(E);
+    for (size_t e = 0; e < E; ++e) {
+      const int s = b->book.costmap_of((int)e);
+      cmaps[e] = s >= 0 ? b->cms[s].get() : c->cmap.cm.get();
+    }
+  }
+  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps]
+  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16, bp = cmaps.size() * sizeof(float*);
   DeviceBuf<char> dbuf;
-  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt));
+  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp));
   char* buf = dbuf;
   ScoreGoal* d_goals = (ScoreGoal*)buf;
   float* d_cost = (float*)(buf + bg);
   float* d_terms = (float*)(buf + bg + bn);
   int32_t* d_col = (int32_t*)(buf + bg + bn + bt);
   int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
+  const float** d_cmaps = (const float**)(buf + bg + bn + bt + bn + bn);
   ScoreArgs a;
   std::memset(&a, 0, sizeof(a));
   a.log = b->log;
@@ -470,7 +687,9 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
   a.cost = d_cost;
   a.terms = d_terms;
   a.collisions = d_col;
+  a.cm_path = bp ? d_cmaps : nullptr;
   hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && bp) e = hipMemcpyAsync(d_cmaps, cmaps.data(), bp, hipMemcpyHostToDevice, c->stream);
   int rc = MPPI_OK;
   if (e == hipSuccess) rc = run_score(c, a);
   if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);

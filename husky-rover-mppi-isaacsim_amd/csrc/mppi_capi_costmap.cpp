@@ -70,6 +70,24 @@ int costmap_stage(CostmapBuffers& sc, const double* obstacles, int32_t n, int32_
 
 }  // namespace
 
+// The build on the context's stream and scratch into `dst` (device, size x size floats), copied to
+// out_host when given; ends synchronised.  mppi_build_costmap and a batch's costmap slots
+// (mppi_batch_build_costmap) share it.
+int mppi::capi::build_costmap_into(mppi_ctx* c, const double* obstacles, int32_t n, int32_t size, double half_width,
+                                   double origin_x, double origin_y, double r_robot, int32_t power, int32_t metric,
+                                   float* dst, float* out_host) {
+  int rc = costmap_check(obstacles, n, size, power, metric);
+  if (rc) return rc;
+  std::vector<double> obs, xs;
+  rc = costmap_stage(c->cmap.scratch, obstacles, n, size, half_width, origin_x, origin_y, r_robot, obs, xs, c->stream);
+  if (rc) return rc;
+  HIP_TRY(launch_costmap_build(c->cmap.scratch.view(), n, size, power, dst, c->stream, metric));
+  if (out_host)
+    HIP_TRY(hipMemcpyAsync(out_host, dst, (size_t)size * size * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
 struct mppi_costmap_builder {
   int device = 0;
   Stream stream;
@@ -94,12 +112,9 @@ int mppi_build_costmap(mppi_ctx* c, const double* obstacles, int32_t n, int32_t 
   const size_t bytes = (size_t)size * size * sizeof(float);
   rc = grow(c->cmap.cm, bytes, c->stream);
   if (rc) return rc;
-  std::vector<double> obs, xs;
-  rc = costmap_stage(c->cmap.scratch, obstacles, n, size, half_width, origin_x, origin_y, r_robot, obs, xs, c->stream);
+  rc = build_costmap_into(c, obstacles, n, size, half_width, origin_x, origin_y, r_robot, power, metric, c->cmap.cm,
+                          out_host);
   if (rc) return rc;
-  HIP_TRY(launch_costmap_build(c->cmap.scratch.view(), n, size, power, c->cmap.cm, c->stream, metric));
-  if (out_host) HIP_TRY(hipMemcpyAsync(out_host, c->cmap.cm, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
   c->cmap.size = size;
   c->cmap.hw = (float)half_width;
   c->cmap.res = res;

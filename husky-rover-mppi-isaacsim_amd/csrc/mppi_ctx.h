@@ -308,6 +308,10 @@ int enqueue_rollout(mppi_ctx* c, int proj, uint64_t step, int mode, const Plan& 
 int enqueue_finish(mppi_ctx* c, const Plan& pl, const mppi_state& st, const double* recs, int n, int mode,
                    double* record_out, bool timed);
 int copy_outputs(mppi_ctx* c, mppi_outputs* out);
+// mppi_capi_costmap.cpp
+int build_costmap_into(mppi_ctx* c, const double* obstacles, int32_t n, int32_t size, double half_width,
+                       double origin_x, double origin_y, double r_robot, int32_t power, int32_t metric, float* dst,
+                       float* out_host);
 // mppi_capi_score.cpp
 int run_score(mppi_ctx* c, const ScoreArgs& a);
 

@@ -193,7 +193,8 @@ hipError_t launch_cdiv_verify(float b, float y, unsigned* bad, hipStream_t st);
 hipError_t launch_noise(uint64_t seed, uint64_t n_base, int64_t k_offset, int blocks, int H, float* eps,
                         hipStream_t st, int max_groups);
 // ---- batched closed-loop episodes (mppi_batch_*) ----
-// E independent episodes over one context's scene and parameters, advanced by three stream-ordered
+// E independent episodes over one context's parameters and (unless an episode holds a scene slot of
+// the batch) scene, advanced by three stream-ordered
 // launches per step (normals, rollout, finish-and-advance) with the loop's state feedback on the GPU.
 // One record per episode in device memory: what a single-context step takes from mppi_state and
 // state_fields() (mppi_capi.cpp) as kernel arguments, plus the loop's own counters.
@@ -217,15 +218,35 @@ struct BatchVariant {
 };
 static_assert(sizeof(BatchVariant) == 56, "BatchVariant layout");
 constexpr int kBatchMaxVariants = 1024;
+// Per-episode scene and trajectory count (mppi_batch_set_dem / _set_costmap / _set_episode_scene /
+// _set_episode_trajectories).  One record per episode, read as one wave-uniform 16-byte load: its
+// DEM and costmap slots (-1: the context's) and its K with blocks = ceil(K / 256) (the context's for
+// an episode that holds none).  The slots' device pointers are three tables indexed by slot, in
+// the same device allocation (BatchSceneTable), so the kernels' arguments carry one pointer.
+struct BatchScene {
+  int dem, cm, K, blocks;
+};
+static_assert(sizeof(BatchScene) == 16, "BatchScene layout");
+constexpr int kBatchMaxDems = 256;       // DEM slots of a batch (heights + normal table each)
+constexpr int kBatchMaxCostmaps = 1024;  // costmap slots of a batch
+struct BatchSceneTable {
+  const float* dem_z[kBatchMaxDems];      // heights of each DEM slot
+  const float4* dem_ntab[kBatchMaxDems];  // its normal table
+  const float* cms[kBatchMaxCostmaps];    // each costmap slot
+  BatchScene rec[1];                      // [E] the episodes' records
+};
 struct BatchArgs {
   // null when no set episode holds a variant: the kernels then read no table, and a batch without
   // variants runs as it did before there were any (the index and the row are two dependent loads
   // at the head of the rollout and of the finish: 0.6 us per step measured at K = 1 000, E = 64)
   const BatchVariant* var;  // [kBatchMaxVariants] the variant table
   const int* ep_var;        // [E] each episode's row of the table, -1: none
-  int proj;                 // the run's projection: that of the episodes without a variant
+  // null while no set episode holds a DEM slot, a costmap slot or a K of its own (the variants' rule:
+  // such a batch pays one scalar compare per kernel)
+  const BatchSceneTable* scene;
   BatchEpisode* ep;  // [E]
   int E, blocks, H;
+  int proj;          // the run's projection: that of the episodes without a variant
   int64_t k_pad;     // blocks * 256
   float* eps;        // [E][blocks][2][H][256] this step's normals
   float* unom;       // [E][2][2H] nominal double buffer
@@ -239,6 +260,8 @@ struct BatchArgs {
   float horizon, rwheel;                  // mppi_params horizon, robot_radius
   int* active_count;                      // pinned host memory: episodes still active
 };
+// (the scene pointer took the place of two paddings: the kernels' argument segment did not grow)
+static_assert(sizeof(BatchArgs) == 136, "BatchArgs layout");
 constexpr int kBatchMaxRecords = 16;  // leaf records per episode: the finish's tree is one LDS pass
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st);
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);

@@ -53,6 +53,9 @@ struct ScoreArgs {
   float* cost;          // [n]
   float* terms;         // [n][4] path, slope, speed, obstacle (16-byte aligned)
   int32_t* collisions;  // [n]
+  // with `log` only: [n] each path's own costmap of cm's geometry (device pointers; an episode's
+  // costmap slot, mppi_batch_score), or null: every path on cm
+  const float* const* cm_path;
 };
 
 hipError_t launch_score(const ScoreArgs& a, hipStream_t st);

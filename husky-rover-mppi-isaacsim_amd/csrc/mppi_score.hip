@@ -216,6 +216,11 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
       }
     }
   }
+  // the costmap the obstacle wave gathers from: the call's, or (LOG) the lane's own path's, loaded once
+  const float* cm = a.cm;
+  if constexpr (LOG) {
+    if (a.cm_path && role == 3 && p < a.n) cm = a.cm_path[p];
+  }
 
   std::conditional_t<LOG, StageLog, Stage<VEC>> r;
   stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, 0, min(CT, Lld), tid);
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     } else {
       const float* q = sm.a[0] + lane * ROW3;
       for (int t = t0; t < te; ++t) {  // critics_warp.py:244-262
-        const float c = a.cm[cm_index(a, q[3 * (t - t0)], q[3 * (t - t0) + 1])];
+        const float c = cm[cm_index(a, q[3 * (t - t0)], q[3 * (t - t0) + 1])];
         if (c > a.thr) {
           acc = acc + a.pen;
           ++col;

@@ -158,6 +158,12 @@ _PROTOS = {
                                              C.POINTER(MppiBatchVariant)]),
     "mppi_batch_set_variants": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchVariant)]),
     "mppi_batch_set_episode_variant": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mppi_batch_set_dem": (C.c_int, [C.c_void_p, C.c_int32, _FP]),
+    "mppi_batch_set_costmap": (C.c_int, [C.c_void_p, C.c_int32, _FP]),
+    "mppi_batch_build_costmap": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_double, C.c_double,
+                                           C.c_double, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_set_episode_scene": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "mppi_batch_set_episode_trajectories": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "mppi_batch_score": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
                                    C.POINTER(MppiPathScores), C.POINTER(C.c_int32)]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
@@ -367,6 +373,8 @@ class Engine:
         self._step_fn = self.lib.mppi_step   # the per-step call, bound once (it sits on the step's host path)
         self._keep = []
         self.async_tail = False
+        self.dem_shape = None       # (rows, cols) of the bound DEM and (size, size) of the costmap:
+        self.costmap_shape = None   # the shape a Batch's scene slots must have
 
     # ------------------------------------------------------------ lifetime
     def close(self):
@@ -398,12 +406,14 @@ class Engine:
         if y_min is None:
             y_min = -half_width
         self._c(self.lib.mppi_set_dem(self.ctx, _fp(Z), rows, cols, x_min, y_min, resolution), "mppi_set_dem")
+        self.dem_shape = (rows, cols)
 
     def set_dem_device(self, ptr, rows, cols, half_width, resolution=None, keepalive=None):
         if resolution is None:
             resolution = 2.0 * half_width / cols
         self._c(self.lib.mppi_set_dem_device(self.ctx, C.c_void_p(int(ptr)), rows, cols, -half_width,
                                              -half_width, resolution), "mppi_set_dem_device")
+        self.dem_shape = (int(rows), int(cols))
         self._keep = [keepalive]
 
     def dem_updated(self):
@@ -416,6 +426,7 @@ class Engine:
         if resolution is None:
             resolution = 2.0 * half_width / size
         self._c(self.lib.mppi_set_costmap(self.ctx, _fp(cm), size, half_width, resolution), "mppi_set_costmap")
+        self.costmap_shape = (size, size)
 
     def build_costmap(self, obstacles, origin, size, half_width, r_robot, power=20, copy_out=True,
                       metric="chamfer"):
@@ -427,6 +438,7 @@ class Engine:
                                             float(origin[0]), float(origin[1]), float(r_robot), int(power),
                                             None if out is None else _fp(out), _metric(metric)),
                 "mppi_build_costmap")
+        self.costmap_shape = (int(size), int(size))
         return out
 
     def rollout_python25d(self, x0, y0, heading, lin_vel, ang_vel, dt, half_width, resolution, bound=20.0):
@@ -680,14 +692,54 @@ class Batch:
         _check(self.lib, self.lib.mppi_batch_create(engine.ctx, self.E, C.byref(h)), "mppi_batch_create")
         self.h = h
 
-    def set_episode(self, e, state: MppiState, seed, variant=-1):
+    def set_episode(self, e, state: MppiState, seed, variant=-1, dem=-1, costmap=-1, trajectories=0):
         """Episode e starts at `state` with Philox key `seed` and runs with row `variant` of the table
-        of set_variants (-1: the engine's params and run()'s proj / policy)."""
+        of set_variants (-1: the engine's params and run()'s proj / policy), on DEM slot `dem` and
+        costmap slot `costmap` (-1: the engine's) with `trajectories` rollouts per step (0: the engine's K)."""
         _check(self.lib, self.lib.mppi_batch_set_episode(self.h, int(e), C.byref(state),
                                                          int(seed) & 0xFFFFFFFFFFFFFFFF),
                "mppi_batch_set_episode")
         _check(self.lib, self.lib.mppi_batch_set_episode_variant(self.h, int(e), int(variant)),
                "mppi_batch_set_episode_variant")
+        _check(self.lib, self.lib.mppi_batch_set_episode_scene(self.h, int(e), int(dem), int(costmap)),
+               "mppi_batch_set_episode_scene")
+        _check(self.lib, self.lib.mppi_batch_set_episode_trajectories(self.h, int(e), int(trajectories)),
+               "mppi_batch_set_episode_trajectories")
+
+    def _slot_array(self, a, shape, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if shape is None:
+            raise RuntimeError(f"{what} slot: the engine has no {what} yet (a slot takes its geometry)")
+        if a.shape != shape:
+            raise ValueError(f"{what} slot: shape {a.shape}, the engine's is {shape}")
+        return a
+
+    def set_dem(self, slot, Z):
+        """DEM slot `slot` holds a copy of Z (the shape and placement of the engine's DEM) and its normal
+        table; None frees the slot."""
+        Z = self._slot_array(Z, self.engine.dem_shape, "DEM")
+        _check(self.lib, self.lib.mppi_batch_set_dem(self.h, int(slot), None if Z is None else _fp(Z)),
+               "mppi_batch_set_dem")
+
+    def set_costmap(self, slot, cm):
+        """Costmap slot `slot` holds a copy of cm (the shape of the engine's costmap); None frees the slot."""
+        cm = self._slot_array(cm, self.engine.costmap_shape, "costmap")
+        _check(self.lib, self.lib.mppi_batch_set_costmap(self.h, int(slot), None if cm is None else _fp(cm)),
+               "mppi_batch_set_costmap")
+
+    def build_costmap(self, slot, obstacles, origin, r_robot, power=20, metric="chamfer", copy_out=False):
+        """Engine.build_costmap with the size and half_width of the engine's costmap, into costmap slot
+        `slot`; returns the map if copy_out."""
+        obs, optr = _obstacles(obstacles)
+        if self.engine.costmap_shape is None:
+            raise RuntimeError("costmap slot: the engine has no costmap yet (a slot takes its geometry)")
+        out = np.empty(self.engine.costmap_shape, np.float32) if copy_out else None
+        _check(self.lib, self.lib.mppi_batch_build_costmap(
+            self.h, int(slot), optr, obs.shape[0], float(origin[0]), float(origin[1]), float(r_robot), int(power),
+            _metric(metric), None if out is None else _fp(out)), "mppi_batch_build_costmap")
+        return out
 
     def set_variants(self, variants):
         """The batch's variant table: a list of MppiBatchVariant or dicts (make_variant's arguments);

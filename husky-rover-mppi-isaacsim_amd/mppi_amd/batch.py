@@ -74,6 +74,44 @@ def variant_dict(proj="3d", **fields):
     return base
 
 
+MAX_DEM_SLOTS, MAX_COSTMAP_SLOTS = 256, 1024    # kBatchMaxDems, kBatchMaxCostmaps (csrc/mppi_kernels.h)
+
+
+def episode_scenes(E, K, dems=None, costmaps=None, episode_dem=None, episode_costmap=None,
+                   episode_trajectories=None):
+    """The per-episode scene arguments of MPPI_Controller.run_batch, checked and filled in:
+    ([dem slot] * E, [costmap slot] * E, [K_e] * E) with -1 / -1 / 0 for the controller's own.
+
+    dems / costmaps: the slots' contents (slot = list index); episode_dem / episode_costmap: E
+    indices into them (-1 or None: the controller's); episode_trajectories: E counts in [1, K]
+    (0 or None: K).  ValueError for a wrong length, an index without a table or outside it, too many
+    slots, or a count outside [1, K].
+    """
+    def indices(name, idx, table, table_name, limit):
+        n = 0 if table is None else len(table)
+        if n > limit:
+            raise ValueError(f"{table_name}: {n} slots, at most {limit}")
+        out = [-1] * E if idx is None else [-1 if i is None else int(i) for i in idx]
+        if len(out) != E:
+            raise ValueError(f"{E} episodes but {len(out)} entries in {name}")
+        if any(i >= 0 for i in out) and n == 0:
+            raise ValueError(f"{name} names slots of `{table_name}`, which is empty")
+        for e, i in enumerate(out):
+            if i < -1 or i >= n:
+                raise ValueError(f"{name}[{e}] = {i} outside the {n} slots of `{table_name}`")
+        return out
+
+    ed = indices("episode_dem", episode_dem, dems, "dems", MAX_DEM_SLOTS)
+    ec = indices("episode_costmap", episode_costmap, costmaps, "costmaps", MAX_COSTMAP_SLOTS)
+    ek = [0] * E if episode_trajectories is None else [0 if k is None else int(k) for k in episode_trajectories]
+    if len(ek) != E:
+        raise ValueError(f"{E} episodes but {len(ek)} entries in episode_trajectories")
+    for e, k in enumerate(ek):
+        if k != 0 and not 1 <= k <= int(K):
+            raise ValueError(f"episode_trajectories[{e}] = {k} outside [1, {int(K)}]")
+    return ed, ec, ek
+
+
 def normalise_heading(hv):
     """Row 0 of heading_sim widened to float64 and divided by sqrt((h0 h0 + h1 h1) + h2 h2) (the sum
     left to right, every operation rounded once), each component rounded to float32."""

@@ -18,6 +18,7 @@ import numpy as np
 import yaml
 
 from . import _lib, scene
+from .batch import episode_scenes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CONFIG = os.path.join(_HERE, "config.yaml")
@@ -328,6 +329,17 @@ class MPPI_Controller:
             cm = cm.reshape(n, n)
         self.engine.set_costmap(cm, self.surface.half_width, self.surface.costmap_resolution)
 
+    def _fill_costmap_slot(self, batch, slot, cm):
+        """One entry of run_batch's `costmaps` into the batch's costmap slot: an array, or a rock list
+        built on the device with the surface's robot radius and costmap metric."""
+        shape = self.engine.costmap_shape
+        if _is_costmap_array(cm, shape):
+            batch.set_costmap(slot, np.asarray(cm, np.float32).reshape(shape))
+            return
+        rocks, origin = (cm["obstacles"], cm.get("origin", (0.0, 0.0))) if isinstance(cm, dict) else (cm, (0.0, 0.0))
+        batch.build_costmap(slot, rocks, origin, self.surface.r_robot, 20,
+                            metric=getattr(self.surface, "costmap_metric", "chamfer"))
+
     def _assign_costmap(self, flat):
         self.surface.costmap = np.asarray(flat, np.float32).reshape(
             self.surface.costmap_size, self.surface.costmap_size)
@@ -477,7 +489,8 @@ class MPPI_Controller:
         print("Number of loops:", self.loop)
 
     def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None,
-                  variants=None, episode_variant=None, score=None):
+                  variants=None, episode_variant=None, score=None, dems=None, costmaps=None, episode_dem=None,
+                  episode_costmap=None, episode_trajectories=None):
         """run() for many episodes at once on this controller's surface and parameters (mppi_batch_*,
         DESIGN.md §3.7): episode e starts at starts[e] = (x, y) with heading headings[e] (normalised
         as Robot does), wheels at rest and the controller's std_dev_u1 / std_dev_u2, and drives to
@@ -493,7 +506,16 @@ class MPPI_Controller:
         (-1 or None: the controller's parameters, `proj` and `policy`).  A weight sweep or the paired
         2D / 3D runs of evaluate_trajectory.py are then one batch.  score: True (the controller's
         weights) or a yardstick (variant or dict): every executed path is scored on the device with
-        that one cost function (mppi_batch_score).
+        that one cost function (mppi_batch_score), each on its own episode's costmap.
+
+        dems: DEMs of the surface's shape, costmaps: costmaps of the surface's costmap shape (2-D, or
+        flat as costmap_wp) or rock lists, built on the device as Surface.create_obstacles_costmap
+        builds them ([[x, y, r], ...] about the origin (0, 0), or dict(obstacles=..., origin=(x, y)));
+        they fill the batch's scene slots in list order.  episode_dem[e] / episode_costmap[e]: the
+        slot episode e runs on (-1 or None: the controller's own surface); episode_trajectories[e]:
+        its number of rollouts per step, in [1, number_of_trajectories] (0 or None: all of them).  A
+        Monte-Carlo over rock fields, the "rocks removed" comparison and the K = 1000 / 500 / 350
+        series are then one batch.
 
         Returns one dict per episode: x, y, z, lin_vel, ang_vel (the lists Robot accumulates: x, y, z
         begin with the start pose and z = 0), loops, reached; with `score` the pair (that list,
@@ -511,6 +533,8 @@ class MPPI_Controller:
             raise ValueError(f"{E} episodes but {len(ev)} variant indices")
         if any(v >= 0 for v in ev) and not variants:
             raise ValueError("episode_variant names rows of `variants`, which is empty")
+        ed, ec, ek = episode_scenes(E, self.number_of_trajectories, dems, costmaps, episode_dem, episode_costmap,
+                                    episode_trajectories)
         if self.engine is None:
             self.warp_setup()
         pol = _lib.make_policy(**(policy or {}))
@@ -518,10 +542,15 @@ class MPPI_Controller:
         try:
             if variants:
                 batch.set_variants(variants)
+            for slot, Z in enumerate(dems or []):
+                Z = np.asarray(Z, np.float32)
+                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
+            for slot, cm in enumerate(costmaps or []):
+                self._fill_costmap_slot(batch, slot, cm)
             for e in range(E):
                 batch.set_episode(e, _lib.make_state(starts[e, 0], starts[e, 1], headings[e], 0.0, 0.0,
                                                      goals[e, 0], goals[e, 1], self.std_dev_u1, self.std_dev_u2),
-                                  seeds[e], ev[e])
+                                  seeds[e], ev[e], ed[e], ec[e], ek[e])
             batch.run(self.max_loops if max_loops is None else int(max_loops), proj, pol)
             out = []
             for e in range(E):
@@ -535,6 +564,14 @@ class MPPI_Controller:
             return out, batch.score(None if score is True else score)
         finally:
             batch.close()
+
+
+def _is_costmap_array(cm, shape):
+    """A costmap given as an array (2-D of `shape`, or flat) rather than as a rock list."""
+    if isinstance(cm, dict):
+        return False
+    a = np.asarray(cm)
+    return a.shape == tuple(shape) or (a.ndim == 1 and a.size == shape[0] * shape[1])
 
 
 def _grid_shape(shape):

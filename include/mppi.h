@@ -307,8 +307,9 @@ int mppi_get_score_ms(mppi_ctx* ctx, double* ms);
 /* ---- batched closed-loop episodes ----
  * MPPI_Controller.run (MPPI_isaac.py:755-806) for E independent episodes at once, the loop's state
  * feedback done on the GPU: the closed-loop campaigns of the thesis (about 2 000 runs of up to 3 500
- * steps) and parameter sweeps.  The episodes share the context's scene (DEM, costmap) and
- * parameters; each has its own start pose, goal, sigmas and Philox seed.  Per step and batch three
+ * steps) and parameter sweeps.  The episodes share the context's parameters and, unless they hold
+ * a variant, a scene slot or a trajectory count of their own (below), its scene (DEM, costmap) and
+ * K; each has its own start pose, goal, sigmas and Philox seed.  Per step and batch three
  * launches on the context stream (normals, rollout, finish-and-advance), no host work in between.
  *
  * The advance rule after a step (float32 unless noted; v, w = element 0 of the filtered optimal
@@ -354,9 +355,10 @@ int  mppi_batch_get_ms(mppi_batch* b, double* ms);  /* HIP-event time of the las
  * The thesis's campaigns vary "weights in the cost function, various terrain constraints, various
  * number of trajectories" (work summarise:52) and alternate a 2D and a 3D run of one task
  * (evaluate_trajectory.py:80-126).  A variant is the set of parameters that one batch can vary per
- * episode: plain kernel scalars that enter no plan, LDS size or shape.  Everything else
- * (num_trajectories, num_iterations, dt, the control and velocity limits, wheel_offset,
- * robot_radius, horizon, the scene, goal_tol, check_every) stays the context's and the run's. */
+ * episode: plain kernel scalars that enter no plan, LDS size or shape.  The scene and the number
+ * of trajectories are per episode too, through the batch's slots (next section).  Everything else
+ * (num_iterations, dt, the control and velocity limits, wheel_offset, robot_radius, horizon,
+ * goal_tol, check_every) stays the context's and the run's. */
 typedef struct mppi_batch_variant {      /* 56 bytes */
   float w_path, w_slope, w_speed, w_obstacle;       /* critics_warp.py:325-329 */
   float collision_threshold, collision_penalty;     /* :251-253 */
@@ -381,10 +383,44 @@ int  mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant*
  * params overridden by the variant, with the variant's projection, advanced by the rule above with
  * the variant's sigma schedule.  Per step the rollout is launched once per projection in use. */
 int  mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant);
+
+/* ---- per-episode scene and trajectory count ----
+ * The campaign's other two axes: "various terrain constraints, various number of trajectories"
+ * (a Monte-Carlo over rock fields, "when removing the rocks"; K = 1000 / 500 / 350).  A batch owns
+ * up to 256 DEM slots (a copy of the heights and its normal table each) and 1024 costmap slots; an
+ * episode may hold one of each and a trajectory count K_e, each independently of the others and of
+ * its variant.  The defaults (-1, -1, 0) are the context's DEM, costmap and num_trajectories,
+ * borrowed at every run as before.  Every step of an episode is bitwise the mppi_step of a context
+ * created with the batch context's params (overridden by the episode's variant) with
+ * num_trajectories = K_e and the same k_offset, after mppi_set_dem(Z of its slot) and
+ * mppi_set_costmap(cm of its slot), with the episode's seed, state and step index; the Philox
+ * address of a trajectory does not depend on K.
+ * A slot takes the context's geometry at the time it is set (DEM: rows, cols, x_min, y_min,
+ * resolution; costmap: size, half_width, resolution), so a DEM and a costmap must be set on the
+ * context first (MPPI_ESTATE).  mppi_batch_run and mppi_batch_score return MPPI_ESTATE, naming the
+ * slot, when an episode in use holds a slot whose geometry is no longer the context's.
+ * z_host [rows * cols] / cm_host [size * size]: copied; setting a live slot again replaces its
+ * contents; NULL frees the slot (MPPI_EINVAL while an episode holds it).  MPPI_EINVAL, naming the
+ * slot, episode or field, for an index out of range, an episode given an empty slot and K_e outside
+ * [1, the context's num_trajectories] (0 resets it).  A failed allocation is MPPI_EHIP with the
+ * size; the slot and the batch stay as they were.  The scene and K_e of an episode outlive
+ * mppi_batch_set_episode, as its variant index does.  All synchronous. */
+int  mppi_batch_set_dem(mppi_batch* b, int32_t slot, const float* z_host);
+int  mppi_batch_set_costmap(mppi_batch* b, int32_t slot, const float* cm_host);
+/* mppi_build_costmap with the context costmap's size and half_width, straight into the slot
+ * (out_host may be NULL).  MPPI_EINVAL if the context costmap's resolution is not
+ * 2 * half_width / size, the builder's own. */
+int  mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacles, int32_t n,
+                              double origin_x, double origin_y, double r_robot, int32_t power,
+                              int32_t metric, float* out_host);
+int  mppi_batch_set_episode_scene(mppi_batch* b, int32_t e, int32_t dem_slot, int32_t costmap_slot);
+int  mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_trajectories);
+
 /* Scores every episode's executed path with one common cost function, on the device
  * (evaluate_trajectory.py:80-126 re-scores each logged run so).  The path of episode e is the log of
  * its most recent run: rows 0 .. steps_last_run-1, waypoint = (x, y, z), lin_vel = v; no wheel
- * arrays, so the slope critic runs on the body path, as mppi_score_paths with NULL wheels.
+ * arrays, so the slope critic runs on the body path, as mppi_score_paths with NULL wheels.  Each
+ * path is scored on its episode's costmap: its costmap slot's, or the context's.
  * yardstick: the weights, collision_threshold and collision_penalty every path is scored with (its
  * other fields are not read); NULL = the context's params.  origins: NULL or [E] states of which x,
  * y, goal_x, goal_y are read; NULL = the episode's position when its most recent run began and the

@@ -41,6 +41,10 @@ int fail(int code, const std::string& msg) {
 // significand (checked exhaustively on the device, 2^23 cases); 0 if none of
 // RN(1/b) and its two neighbours qualifies.  Cached per divisor.
 int verified_reciprocal(mppi_ctx* c, float b, float* y_out) {
+  if (!c->use_cdiv) {  // mppi_set_option "verified_reciprocal" 0
+    *y_out = 0.0f;
+    return MPPI_OK;
+  }
   uint32_t key;
   std::memcpy(&key, &b, 4);
   auto it = c->cdiv_cache.find(key);
@@ -1426,6 +1430,16 @@ int mppi_set_option(mppi_ctx* c, const char* name, int64_t value) {
     c->colfin = value == 0;
     return MPPI_OK;
   }
+  if (n == "verified_reciprocal") {  // test hook: 0 puts every cell index on the IEEE division (rinv_res = 0)
+    if (value < 0 || value > 1) return fail(MPPI_EINVAL, "verified_reciprocal must be 0 or 1");
+    HIP_TRY(hipSetDevice(c->device));
+    c->use_cdiv = value != 0;
+    if (c->dem.Z)
+      if (int rc = verified_reciprocal(c, c->dem.res, &c->dem.rinv_res)) return rc;
+    if (c->cmap.cm)
+      if (int rc = verified_reciprocal(c, c->cmap.res, &c->cmap.rinv_res)) return rc;
+    return MPPI_OK;
+  }
   if (n == "server_exit_after") {  // test hook: the next server launch's head leaves after this many commands
     if (value < 0 || value > 1000000) return fail(MPPI_EINVAL, "server_exit_after must be in [0, 1e6]");
     c->srv.exit_after = (unsigned)value;
@@ -1558,11 +1572,12 @@ int mppi_get_chain_clock(mppi_ctx* c, double* out, int32_t n) {
 int mppi_get_launch_info(mppi_ctx* c, int64_t* info, int32_t n) {
   if (!c || !info) return fail(MPPI_EINVAL, "null argument");
   const Plan& pl = c->last.plan;
-  const int64_t v[18] = {0, pl.block, pl.blocks, pl.W, pl.Wr, (int64_t)pl.lds_bytes, c->last.fin_kind,
+  const int64_t v[19] = {0, pl.block, pl.blocks, pl.W, pl.Wr, (int64_t)pl.lds_bytes, c->last.fin_kind,
                          c->last.fin_P, c->last.fin_ncol, c->last.fin_groups, pl.ucache_steps, c->last.resident ? 1 : 0,
                          c->srv.launches, c->srv.steps, c->srv.failed, c->srv.relaunches, c->srv.fallbacks,
-                         c->srv.cadence_steps};
-  for (int i = 0; i < n && i < 18; ++i) info[i] = v[i];
+                         c->srv.cadence_steps,
+                         (c->dem.rinv_res != 0.0f ? 1 : 0) | (c->cmap.rinv_res != 0.0f ? 2 : 0)};
+  for (int i = 0; i < n && i < 19; ++i) info[i] = v[i];
   return MPPI_OK;
 }
 

@@ -266,6 +266,9 @@ struct mppi_ctx {
   int roles = -1;     // rollout kernel: -1 auto (role split at <= 1 workgroup per CU), 0 pair, 1 roles (MPPI_ROLES)
   mppi::DeviceBuf<unsigned> cdiv_bad;  // device counter for launch_cdiv_verify
   std::unordered_map<uint32_t, float> cdiv_cache;  // divisor bits -> verified y (0: none)
+  // test hook mppi_set_option("verified_reciprocal"): false makes verified_reciprocal hand out 0,
+  // so every cell index of the DEM and the costmap takes the IEEE division
+  bool use_cdiv = true;
   mppi::capi::Dem dem;
   mppi::capi::Costmap cmap;
   mppi::capi::StepBuffers sb;

@@ -595,12 +595,12 @@ class Engine:
         return t.value, n.value
 
     def launch_info(self):
-        info = (C.c_int64 * 18)()
-        self._c(self.lib.mppi_get_launch_info(self.ctx, info, 18), "mppi_get_launch_info")
+        info = (C.c_int64 * 19)()
+        self._c(self.lib.mppi_get_launch_info(self.ctx, info, 19), "mppi_get_launch_info")
         keys = ("reserved", "block", "blocks", "window_cols", "window_rows", "lds_bytes", "finish_kind",
                 "finish_records", "finish_ncol", "finish_groups", "ucache_steps", "resident",
                 "server_launches", "server_steps", "server_failed_steps", "server_relaunches",
-                "server_fallbacks", "cadence_steps")
+                "server_fallbacks", "cadence_steps", "verified_reciprocals")
         return dict(zip(keys, [int(v) for v in info]))
 
     def server_time(self):

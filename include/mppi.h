@@ -105,6 +105,10 @@ int mppi_set_stream(mppi_ctx* ctx, void* hip_stream);
 /* self.Z_wp = wp.array(surface.Z.flatten()) (MPPI_isaac.py:460): copies the
  * row-major rows x cols DEM to the device.  x_min = y_min = -half_width and
  * resolution = 2*half_width/grid_size as in the launch args (:560-564).
+ * Any other placement is allowed, rows and cols need not be equal: the cell of
+ * (x, y) is column trunc((x - x_min) / resolution) and row
+ * -trunc((y + y_min) / resolution), both clamped into the map, so column 0
+ * starts at x = x_min and row 0 lies at y = -y_min with y falling as rows grow.
  * rows * cols < 2^29 (MPPI_EINVAL otherwise). */
 int mppi_set_dem(mppi_ctx* ctx, const float* z_host, int32_t rows, int32_t cols, float x_min,
                  float y_min, float resolution);
@@ -478,6 +482,12 @@ int mppi_set_timing(mppi_ctx* ctx, int32_t enable);
  *                        rollout / the finish.  Results are the same bits either way.
  *   "record_tree_finish" 1: the record-tree finish (mppi_finish_kernel) at every record count
  *                        (default 0: the column-split finish wherever its shape fits).
+ *   "verified_reciprocal" test hook: 0 makes every cell index of the DEM and the costmap take the
+ *                        IEEE division (the kernels' arm for a resolution with no verified
+ *                        reciprocal, which no resolution tried so far reaches): it applies to the
+ *                        bound DEM and costmap and to every later mppi_set_dem* / mppi_set_costmap /
+ *                        mppi_build_costmap; 1 (default) restores the verified reciprocals.  Results
+ *                        are the same bits either way.
  *   "server_exit_after"  test hook: the next server launch leaves at its poll after serving this
  *                        many steps, whether or not the next step was posted (0: off, default);
  *                        that step is served by a relaunch. */
@@ -496,7 +506,10 @@ int mppi_get_tail_timing(mppi_ctx* ctx, double* tail_ms, int64_t* launches);
  * steps served / failed steps so far (mppi_set_option "resident"); [15] = commands posted to a
  * server that was leaving on its idle limit and served by a relaunch (included in [12]); [16] =
  * failed server steps rerun as separate launches; [17] = steps the server could have run that ran as
- * separate launches because the call was not back-to-back ("resident" 1).  Up to 18 values. */
+ * separate launches because the call was not back-to-back ("resident" 1); [18] = which cell
+ * indices the next launch divides by a verified reciprocal: 1 the bound DEM's, 2 the bound
+ * costmap's, 3 both, 0 neither (the IEEE division; mppi_set_option "verified_reciprocal").
+ * Up to 19 values. */
 int mppi_get_launch_info(mppi_ctx* ctx, int64_t* info, int32_t n);
 
 /* Shader clock of the last sampled 3D rollout, from the chain wave of trajectories 0..63

@@ -92,13 +92,15 @@ def oracle_loop(K, H, scene, st, seed, n_steps, proj="3d", pol=RUN, params=None)
     return _result(rows, st, u1, u2, i, pol)
 
 
-def engine_loop(K, H, Z, hw, cm, st, seed, n_steps, proj="3d", pol=RUN):
-    """Reference B: a fresh Engine at its default options, stepped from the host."""
+def engine_loop(K, H, Z, hw, cm, st, seed, n_steps, proj="3d", pol=RUN, make_engine=None):
+    """Reference B: a fresh Engine at its default options, stepped from the host.  make_engine(seed), if
+    given, builds it instead, scene bound (other parameters or grid geometry; Z, hw, cm are then unused)."""
     from mppi_amd import _lib
-    eng = _lib.Engine(_lib.make_params(K, H, seed=seed), 0)
+    eng = make_engine(seed) if make_engine else _lib.Engine(_lib.make_params(K, H, seed=seed), 0)
     try:
-        eng.set_dem(Z, hw)
-        eng.set_costmap(cm, hw)
+        if not make_engine:
+            eng.set_dem(Z, hw)
+            eng.set_costmap(cm, hw)
         r = float(eng.params.robot_radius)
         rows = []
         i = 0

@@ -38,6 +38,35 @@ def engine_for(K, H, Z, hw, cm, st: R.State, seed=42, k_offset=0, device=0, **kw
     return eng
 
 
+def scene_for(Z, cm, half_width, resolution=None, x_min=None, y_min=None, cm_half_width=None, cm_resolution=None):
+    """The oracle's scene for a DEM of any shape and placement.  half_width is the DEM's (resolution
+    2 * half_width / cols, x_min = y_min = -half_width unless given); the costmap lies over
+    +-cm_half_width (default the DEM's) at cm_resolution (default 2 * cm_half_width / size)."""
+    Z = np.asarray(Z)
+    return R.Scene(Z, half_width if cm_half_width is None else cm_half_width, cm,
+                   resolution=2.0 * half_width / Z.shape[1] if resolution is None else resolution,
+                   costmap_resolution=cm_resolution,
+                   x_min=-half_width if x_min is None else x_min, y_min=-half_width if y_min is None else y_min)
+
+
+def bind_scene(eng, sc: R.Scene):
+    """Hand the engine the very numbers the oracle's scene holds (already float32, so nothing rounds twice)."""
+    eng.set_dem(sc.Z, resolution=float(sc.res), x_min=float(sc.x_min), y_min=float(sc.y_min))
+    eng.set_costmap(sc.costmap, float(sc.hw), float(sc.res_c))
+
+
+def engine_on(K, H, Z, cm, st: R.State, half_width, seed=42, k_offset=0, device=0, resolution=None, x_min=None,
+              y_min=None, cm_half_width=None, cm_resolution=None, **kw):
+    """engine_for on any grid geometry (scene_for's arguments): (engine, the matching R.Scene).  Both sides
+    are built from one description, so a case cannot give the engine one scene and the oracle another."""
+    from mppi_amd import _lib
+    sc = scene_for(Z, cm, half_width, resolution, x_min, y_min, cm_half_width, cm_resolution)
+    eng = _lib.Engine(_lib.make_params(K, H, k_offset=k_offset, seed=seed, **kw), device)
+    bind_scene(eng, sc)
+    eng.set_state(state_for(st))
+    return eng, sc
+
+
 def state_for(st: R.State):
     from mppi_amd import _lib
     return _lib.make_state(st.x, st.y, st.heading, st.left_wheel_speed, st.right_wheel_speed,

@@ -7,6 +7,7 @@ step counts, `reached`) with the closed loops of tests/batch_refs.py on the C1-C
 both with the advance rule written out in the test helpers and the raw row-0 heading passed on.
 """
 import ctypes
+import dataclasses
 import functools
 
 import numpy as np
@@ -108,6 +109,51 @@ def _ref_b(K, H, st, seed, n, proj="3d", pol=B.RUN):
 def _ref_a(K, H, st, seed, n, proj="3d", pol=B.RUN):
     from helpers import c3_scene, oracle_scene
     return B.oracle_loop(K, H, oracle_scene(*c3_scene()), dict(st), seed, n, proj, pol)
+
+
+@pytest.mark.parametrize("which", ["large_angle", "nonsquare"])
+def test_off_default_parameters_and_geometry(which):
+    """2 episodes x 3 steps on a context created with test_gpu_param_space's large-angle parameters
+    (the batch fills the rollout's small_angle itself), and on its 120 x 200 DEM with x_min != -y_min,
+    from the map's lower left corner: equal to the engine-stepped loop and to the oracle's."""
+    _gpu()
+    import helpers as hp
+    import test_gpu_param_space as PS
+    from mppi_amd import _lib
+    K, H, n = 256, 16, 3
+    if which == "large_angle":
+        c, starts = PS.LARGE_ANGLE, [((-12.0, -3.0), (1.0, 0.0, 0.0)), ((3.0, 4.0), (0.0, -1.0, 0.0))]
+        assert not PS._small_angle_rule(c)
+    else:
+        c, starts = PS.GEOMETRY["nonsquare_corner"], [((-29.9, -19.5), (-1.0, 0.0, 0.0)), ((-29.5, -19.9), (0.0, -1.0, 0.0))]
+    sc, params = PS._scene(c.scene), dict(c.params)
+
+    def make_engine(seed):
+        eng = _lib.Engine(_lib.make_params(K, H, seed=seed, **params), 0)
+        hp.bind_scene(eng, sc)
+        return eng
+
+    episodes = []
+    for e, (start, heading) in enumerate(starts):
+        st = B.start_state(start, PS.GOAL, heading, s1=0.8, s2=0.8)
+        st["wl"], st["wr"] = np.float32(0.6), np.float32(0.8)
+        episodes.append((st, 11 + e))
+    eng = make_engine(42)
+    try:
+        batch = _lib.Batch(eng, len(episodes))
+        for e, (st, seed) in enumerate(episodes):
+            batch.set_episode(e, _mppi_state(st), seed)
+        batch.run(n, "3d", _lib.make_policy(**B.RUN))
+        got = [_collect(batch, e) for e in range(len(episodes))]
+        batch.close()
+    finally:
+        eng.close()
+    p = dataclasses.replace(c.oracle_params(), K=K, H=H)
+    for e, (st, seed) in enumerate(episodes):
+        assert got[e]["steps"] == n
+        _same(got[e], B.engine_loop(K, H, None, None, None, dict(st), seed, n, make_engine=make_engine),
+              f"{which} episode {e} vs B")
+        _same(got[e], B.oracle_loop(K, H, sc, dict(st), seed, n, params=p), f"{which} episode {e} vs A")
 
 
 def _main_episodes():

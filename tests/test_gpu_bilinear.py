@@ -14,8 +14,11 @@ from oracle import mppi_ref as R
 pytestmark = pytest.mark.gpu
 
 
-def _oracle_heights(Z, hw, x, y):
-    sc = R.Scene(Z, hw, np.zeros((4, 4), np.float32))
+NON_SQUARE = dict(resolution=0.25, x_min=-30.0, y_min=-10.0)   # 120 x 200: x in [-30, 20], y in [-20, 10]
+
+
+def _oracle_heights(Z, hw, x, y, **geo):
+    sc = hp.scene_for(Z, np.zeros((4, 4), np.float32), hw, **geo)
     q = R.get_corners_heights(sc, x, y)
     return R.bilinear(x, y, q, sc.res)
 
@@ -29,29 +32,44 @@ def _points(n, hw, seed, margin=1.5):
     return x, y
 
 
-def _engine(Z, hw):
+def _engine(Z, hw, **geo):
     from mppi_amd import _lib
     eng = _lib.Engine(_lib.make_params(256, 8), 0)
-    eng.set_dem(Z, hw)
+    eng.set_dem(Z, hw, **geo)
     return eng
 
 
-@pytest.mark.parametrize("which", ["c3", "odd", "few_tiles"])
+@pytest.mark.parametrize("which", ["c3", "odd", "few_tiles", "non_square"])
 def test_bilinear_query_and_tiled_match_oracle(which):
     import torch
-    if which == "odd":   # ragged map: rows/cols not multiples of the 128-cell tile
+    geo = {}
+    n = 200_003
+    if which == "non_square":   # rows != cols, x_min != -y_min: 1 x 2 tiles, both partial, fewer than a row of 128
+        rng = np.random.default_rng(5)
+        Z = rng.normal(size=(120, 200)).astype(np.float32)
+        hw, geo, n = 30.0, NON_SQUARE, 20_003
+    elif which == "odd":   # ragged map: rows/cols not multiples of the 128-cell tile
         rng = np.random.default_rng(3)
         Z = rng.normal(size=(203, 203)).astype(np.float32)
         hw = 10.15
     else:
         Z, hw, _ = hp.c3_scene()
-    n = 200_003
     x, y = _points(n, hw, seed=11)
+    if which == "non_square":   # the map's own extent and 15 m around it; its corners, edges and just past them
+        rng = np.random.default_rng(12)
+        x[8:] = rng.uniform(-45.0, 35.0, n - 8).astype(np.float32)
+        y[8:] = rng.uniform(-35.0, 25.0, n - 8).astype(np.float32)
+        x[8:16] = np.array([-30.0, 20.0, -30.0, 20.0, 19.875, 20.125, -30.125, -5.0], np.float32)
+        y[8:16] = np.array([10.0, 10.0, -20.0, -20.0, -19.875, -20.125, 10.125, -5.0], np.float32)
+        sc = hp.scene_for(Z, np.zeros((4, 4), np.float32), hw, **geo)
+        i, j = R.dem_cell(sc, x, y)
+        assert i.min() == -1 and i.max() == 200 and j.min() == -1 and j.max() == 120   # out on all four sides
+        assert ((i >= 0) & (i < 200) & (j >= 0) & (j < 120)).mean() > 0.3
     if which == "few_tiles":   # every query in 4 tiles: long runs per sorted block
         x = (x % np.float32(5.0)).astype(np.float32)
         y = (y % np.float32(5.0)).astype(np.float32)
-    want = _oracle_heights(Z, hw, x, y)
-    eng = _engine(Z, hw)
+    want = _oracle_heights(Z, hw, x, y, **geo)
+    eng = _engine(Z, hw, **geo)
     xd = torch.from_numpy(x).cuda()
     yd = torch.from_numpy(y).cuda()
     hd = torch.empty_like(xd)

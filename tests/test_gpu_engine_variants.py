@@ -213,10 +213,12 @@ def test_option_validation():
     eng = _engine(2048, 8)
     try:
         for name, bad in (("resident", 3), ("resident", -1), ("eps_after", 2), ("eps_after", -2),
-                          ("resident_idle_us", 50), ("finish_wait_ticks", -1), ("no_such_option", 1)):
+                          ("resident_idle_us", 50), ("finish_wait_ticks", -1), ("verified_reciprocal", 2),
+                          ("verified_reciprocal", -1), ("no_such_option", 1)):
             with pytest.raises(RuntimeError, match="mppi_set_option"):
                 eng.set_option(name, bad)
-        for name, good in (("resident", 0), ("eps_after", -1), ("eps_after", 0), ("eps_after", 1)):
+        for name, good in (("resident", 0), ("eps_after", -1), ("eps_after", 0), ("eps_after", 1),
+                           ("verified_reciprocal", 0), ("verified_reciprocal", 1)):
             eng.set_option(name, good)
         eng.step("3d", 0, copy=False)
     finally:

@@ -146,6 +146,45 @@ def test_small_odd_costmap_needs_no_dem(goal):
         eng.close()
 
 
+@pytest.mark.parametrize("costmap", ["small", "one_cell"])
+def test_dumped_rollouts_of_a_non_square_dem(costmap):
+    """The rollouts a step on the 120 x 200 DEM (x_min = -30, y_min = -10) dumps, scored on a 50 x 50
+    costmap over +-8 m and on a 1 x 1 costmap: as dumped (from the DEM's lower left corner every waypoint
+    is outside the small costmap and clamps to one cell) and moved so that they straddle its border."""
+    import test_gpu_param_space as PS
+    from mppi_amd import _lib
+    c = PS.GEOMETRY["nonsquare_corner"]
+    dem, st, p = PS._scene(c.scene), c.oracle_state(), c.oracle_params()
+    cm = PS._costmap(50) if costmap == "small" else np.full((1, 1), 0.996, F32)
+    sc = hp.scene_for(dem.Z, cm, 30.0, resolution=0.25, x_min=-30.0, y_min=-10.0, cm_half_width=8.0)
+    eng = _lib.Engine(_lib.make_params(c.K, c.H, **{"seed": PS.SEED, **dict(c.params)}), 0)
+    try:
+        hp.bind_scene(eng, dem)
+        eng.set_state(hp.state_for(st))
+        eng.step("3d", 0, copy=False)
+        d = eng.dump()
+        part = PS._ref(c)[0]["parts"][0]
+        for name in ("traj", "lw", "rw", "v"):
+            assert np.array_equal(d[name], part[name]), hp.mismatch_report(f"dump {name}", d[name], part[name])
+        eng.set_costmap(cm, 8.0)
+        for shift in ((0.0, 0.0), (21.9, 11.9)):
+            traj, lw, rw = (a.copy() for a in (d["traj"], d["lw"], d["rw"]))
+            for a in (traj, lw, rw):
+                a[..., :2] += np.asarray(shift, F32)
+            x, y = traj[..., 0], traj[..., 1]
+            out = (np.abs(x) >= 8.0) | (np.abs(y) >= 8.0)
+            if shift == (0.0, 0.0):
+                assert out.all()
+            else:
+                assert (out.any(1) & ~out.all(1)).mean() > 0.05, "no path crosses the costmap's border"
+            want = oracle_scores(p, sc, st, traj, lw, rw, d["v"])
+            if costmap == "one_cell":
+                assert (want[2] == c.H).all()      # the one cell is above the threshold: every waypoint collides
+            check(eng.score_paths(traj, d["v"], lw, rw, state=hp.state_for(st)), want, f"{costmap} {shift}")
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("n,L", [(65, 67), (64, 130), (1, 3), (5, 4)])
 def test_body_slope_mode(scorer, n, L):
     """Without wheel arrays the slope critic runs on the body path: the oracle with lw = rw = traj."""

@@ -7,6 +7,10 @@
 // episode's state lives in its BatchEpisode record (device memory), read with wave-uniform loads
 // where a single-context step reads kernel arguments.  No workgroup waits for another or for the
 // host (apart from roles_body's own in-workgroup LDS rings).
+//
+// The task queue (mppi_batch_run_tasks): the finish kernel's campaign form lets the lane whose task
+// ended claim the next task of a list in device memory (campaign_claim / campaign_refill); the one
+// word two workgroups of a launch share is the list's counter, taken with an agent-scope atomic add.
 #pragma once
 
 // The normals of every active episode's current step, [blocks][2][H][256] per episode, addressed as
@@ -98,18 +102,127 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
   roles_body<256, PROJ, 0, false, false>(a, (int)blockIdx.x, nullptr);
 }
 
+// The claim rule of the task queue, run by one thread of lane e whose task is over (or that has
+// none yet: the first fill).  Takes the next index of the list with one agent-scope atomic add; a
+// task whose start already passes the goal test takes no step: its result is written at once
+// (steps 0, reached) and the lane claims again.  A claimed task is loaded into the lane: its
+// start, the critics' scalar parts by the float32 operations of state_fields() (as the advance
+// computes them), seed, Philox step 0, half 0 of the nominal double buffer, no rows, and the lane's
+// variant index and scene record, which the next step's kernels read.  With the list exhausted the
+// lane goes inactive and leaves the pinned count.  Returns whether a task was loaded (the caller
+// then zeroes the lane's nominal double buffer).
+__device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep) {
+  for (;;) {
+    const int i = __hip_atomic_fetch_add(q.next_task, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (i >= q.n) {
+      ep->active = 0;
+      q.lane[e] = BatchLane{-1, 0, 0};
+      __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return false;
+    }
+    const BatchTask* t = q.tasks + i;
+    const float x = t->x0, y = t->y0, gx = t->gx, gy = t->gy;
+    if (!(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol)) {
+      BatchTaskResult* r = q.res + i;
+      r->x0 = x;
+      r->y0 = y;
+      r->h0x = t->h0x;
+      r->h0y = t->h0y;
+      r->h0z = t->h0z;
+      r->wl = t->wl;
+      r->wr = t->wr;
+      r->gx = gx;
+      r->gy = gy;
+      r->s1 = t->s1;
+      r->s2 = t->s2;
+      r->steps = 0;
+      r->reached = 1;
+      r->flags = 3;
+      continue;
+    }
+    ep->x0 = x;
+    ep->y0 = y;
+    ep->h0x = t->h0x;
+    ep->h0y = t->h0y;
+    ep->h0z = t->h0z;
+    ep->wl = t->wl;
+    ep->wr = t->wr;
+    ep->gx = gx;
+    ep->gy = gy;
+    ep->s1 = t->s1;
+    ep->s2 = t->s2;
+    {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
+      const float xd = gx - x;
+      const float yd = gy - y;
+      const float dist = sqrtf(xd * xd + yd * yd);
+      const float horizon = b.horizon;
+      ep->pf_far = dist > horizon ? 1 : 0;
+      ep->igx = x + (xd * horizon) / (dist + 1e-6f);
+      ep->igy = y + (yd * horizon) / (dist + 1e-6f);
+      ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
+      ep->speed_on = (dist < 2.0f) ? 0 : 1;
+    }
+    ep->active = 1;
+    ep->cur = 0;
+    ep->seed = t->seed;
+    ep->step = 0;
+    ep->steps_run = 0;
+    ep->reached = 0;
+    q.lane[e] = BatchLane{i, t->max_steps, t->log_base};
+    q.ep_var[e] = t->variant;
+    q.rec[e] = t->scene;
+    q.res[i].flags = 1;
+    return true;
+  }
+}
+
+// The whole workgroup of lane e (nthreads threads, `got`: one int of LDS): thread 0 claims when
+// the lane's task is `ended` (its own knowledge; the others pass anything), the decision goes
+// through LDS, and on a new task every thread zeroes its share of both halves of the lane's nominal
+// double buffer (what mppi_batch_set_episode does with a memset).  Every thread of the workgroup
+// calls this: the branch is uniform, the barrier is not inside it.
+__device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep,
+                                                bool ended, int tid, int nthreads, int* got) {
+  if (tid == 0) *got = (ended && campaign_claim(b, q, e, ep)) ? 1 : 0;
+  __syncthreads();
+  if (*got) {
+    float* u = b.unom + (size_t)e * 4 * b.H;
+    for (int j = tid; j < 4 * b.H; j += nthreads) u[j] = 0.0f;
+  }
+}
+
 // One workgroup per episode: the binary tree over its leaf records (tree_reduce of the oracle: the
 // count padded to a power of two with empty records; one aligned group of 16 with the empty members
 // passing their partners through, as the last pass of mppi_finish_kernel), the mode-2 phase 2 (u_opt
 // into the other half of the nominal double buffer, the filtered v / w, row 0 of the optimal
 // rollout), then one lane advances the episode by the closed loop's rule (MPPI_Controller.run,
 // MPPI_isaac.py:769-784; mppi_amd/batch.py advance_state is the same arithmetic on the host).
-__global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b) {
+//
+// CAMPAIGN (mppi_batch_run_tasks): the episode is a lane working through the task list `q`.  Its
+// row goes to its task's rows of the log arena, and when the task ends (goal test passed, or the
+// row count reaches the task's cap) the advance lane writes the task's result and the workgroup
+// refills the lane (campaign_refill above) instead of going inactive.  The campaign form is the
+// instantiation with the queue as its own third kernel argument; the plain form takes the two
+// arguments it always took (BatchArgs does not grow).
+__device__ __forceinline__ const BatchCampaign* queue_of() { return nullptr; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchCampaign& q) { return &q; }
+template <class... Queue>
+__global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
+                                                                         const Queue... queue) {
+  static_assert(sizeof...(Queue) <= 1, "at most the one queue");
+  constexpr bool CAMPAIGN = sizeof...(Queue) == 1;
+  const BatchCampaign* q = queue_of(queue...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
   if (!ep->active) return;
   const int tid = threadIdx.x;
+  BatchLane ln{};
+  int lane_steps = 0;  // CAMPAIGN: loaded here, off the advance lane's serial path
+  if constexpr (CAMPAIGN) {
+    ln = q->lane[e];
+    lane_steps = q->lane_steps[e];
+  }
   FinishArgs f = f_in;
   const int H = f.H, E = 2 * H + 2;
   float sigma_base = b.sigma_base, sigma_div = b.sigma_div;
@@ -186,58 +299,92 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   finish_phase2(f, ures, smem_raw, tid, FIN_THREADS);
   // ---------------- (3) advance (finish_phase2 ends with every output store complete and a barrier;
   // the outputs were written through, so agent-scope loads see them)
-  if (tid != 0) return;
-  auto ld = [&](int i) __attribute__((always_inline)) {
-    return __hip_atomic_load(f.out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  const float v = ld(2 * H), w = ld(3 * H);
-  const float x = ld(4 * H), y = ld(4 * H + 1), z = ld(4 * H + 2);
-  // heading: row 0 widened to float64 and divided by its norm ((a a + b b) + c c, no fma), each
-  // component rounded to float32 (robot.heading_vector / np.linalg.norm, MPPI_isaac.py:493)
-  const double d0 = (double)ld(4 * H + 3), d1 = (double)ld(4 * H + 4), d2 = (double)ld(4 * H + 5);
-  const double nn = __builtin_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
-  const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
-  if (row < b.log_cap) {
-    float* lg = b.log + ((size_t)e * b.log_cap + row) * 8;
-    lg[0] = x;
-    lg[1] = y;
-    lg[2] = z;
-    lg[3] = hx;
-    lg[4] = hy;
-    lg[5] = hz;
-    lg[6] = v;
-    lg[7] = w;
+  if constexpr (!CAMPAIGN) {
+    if (tid != 0) return;
   }
-  const float ww = (w * w) / sigma_div;
-  const float half = (w * b.rwheel) / 2.0f;
-  ep->x0 = x;
-  ep->y0 = y;
-  ep->h0x = hx;
-  ep->h0y = hy;
-  ep->h0z = hz;
-  ep->wl = v - half;
-  ep->wr = v + half;
-  ep->s1 = fmaxf(sigma_base, sigma_base - ww);
-  ep->s2 = fmaxf(sigma_base, sigma_base + ww);
-  {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
-    const float xd = gx - x;
-    const float yd = gy - y;
-    const float dist = sqrtf(xd * xd + yd * yd);
-    const float horizon = b.horizon;
-    ep->pf_far = dist > horizon ? 1 : 0;
-    ep->igx = x + (xd * horizon) / (dist + 1e-6f);
-    ep->igy = y + (yd * horizon) / (dist + 1e-6f);
-    ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
-    ep->speed_on = (dist < 2.0f) ? 0 : 1;
+  bool ended = false;  // CAMPAIGN, advance lane: the task is over
+  if (!CAMPAIGN || tid == 0) {
+    auto ld = [&](int i) __attribute__((always_inline)) {
+      return __hip_atomic_load(f.out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    const float v = ld(2 * H), w = ld(3 * H);
+    const float x = ld(4 * H), y = ld(4 * H + 1), z = ld(4 * H + 2);
+    // heading: row 0 widened to float64 and divided by its norm ((a a + b b) + c c, no fma), each
+    // component rounded to float32 (robot.heading_vector / np.linalg.norm, MPPI_isaac.py:493)
+    const double d0 = (double)ld(4 * H + 3), d1 = (double)ld(4 * H + 4), d2 = (double)ld(4 * H + 5);
+    const double nn = __builtin_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+    const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
+    if (row < (CAMPAIGN ? ln.max_steps : b.log_cap)) {
+      float* lg = CAMPAIGN ? q->log + ((size_t)ln.log_base + row) * 8 : b.log + ((size_t)e * b.log_cap + row) * 8;
+      lg[0] = x;
+      lg[1] = y;
+      lg[2] = z;
+      lg[3] = hx;
+      lg[4] = hy;
+      lg[5] = hz;
+      lg[6] = v;
+      lg[7] = w;
+    }
+    const float ww = (w * w) / sigma_div;
+    const float half = (w * b.rwheel) / 2.0f;
+    ep->x0 = x;
+    ep->y0 = y;
+    ep->h0x = hx;
+    ep->h0y = hy;
+    ep->h0z = hz;
+    ep->wl = v - half;
+    ep->wr = v + half;
+    ep->s1 = fmaxf(sigma_base, sigma_base - ww);
+    ep->s2 = fmaxf(sigma_base, sigma_base + ww);
+    {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
+      const float xd = gx - x;
+      const float yd = gy - y;
+      const float dist = sqrtf(xd * xd + yd * yd);
+      const float horizon = b.horizon;
+      ep->pf_far = dist > horizon ? 1 : 0;
+      ep->igx = x + (xd * horizon) / (dist + 1e-6f);
+      ep->igy = y + (yd * horizon) / (dist + 1e-6f);
+      ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
+      ep->speed_on = (dist < 2.0f) ? 0 : 1;
+    }
+    ep->cur = cur_buf ^ 1;
+    ep->step = ep->step + 1;
+    ep->steps_run = row + 1;
+    const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
+    if constexpr (CAMPAIGN) {
+      q->lane_steps[e] = lane_steps + 1;
+      ended = reached || row + 1 >= ln.max_steps;
+      if (ended) {
+        BatchTaskResult* r = q->res + ln.task;
+        r->x0 = x;
+        r->y0 = y;
+        r->h0x = hx;
+        r->h0y = hy;
+        r->h0z = hz;
+        r->wl = v - half;
+        r->wr = v + half;
+        r->gx = gx;
+        r->gy = gy;
+        r->s1 = fmaxf(sigma_base, sigma_base - ww);
+        r->s2 = fmaxf(sigma_base, sigma_base + ww);
+        r->steps = row + 1;
+        r->reached = reached ? 1 : 0;
+        r->flags = 3;
+      }
+    } else if (reached) {
+      ep->active = 0;
+      ep->reached = 1;
+      __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
-  ep->cur = cur_buf ^ 1;
-  ep->step = ep->step + 1;
-  ep->steps_run = row + 1;
-  if (!(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol)) {
-    ep->active = 0;
-    ep->reached = 1;
-    __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if constexpr (CAMPAIGN) campaign_refill(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw));
+}
+
+// The first fill of a campaign: every lane claims as a finishing lane does.  Grid E, one wave each.
+__global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b, const BatchCampaign q) {
+  __shared__ int got;
+  const int e = blockIdx.x;
+  campaign_refill(b, q, e, b.ep + e, true, (int)threadIdx.x, 64, &got);
 }
 
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
@@ -258,6 +405,17 @@ hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t
 }
 
 hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b);
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_claim_kernel, dim3((unsigned)b.E), dim3(64), 0, st, b, q);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
+                                        hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, q);
   return hipGetLastError();
 }

@@ -104,6 +104,13 @@ class BatchSceneBook {
     return kSceneOk;
   }
   void mark_set(int e) { set_[(size_t)e] = 1; }  // mppi_batch_set_episode: the episode is in use
+  // A campaign used the episodes as lanes (mppi_batch_run_tasks): none is in use until it is set
+  // again.  Their slots and K_e stay.
+  void mark_all_unset() { set_.assign(set_.size(), 0); }
+  // Does the live slot hold geometry `g`?  (The task list's slots: mppi_batch_tasks.h.)
+  bool slot_has_geometry(SceneKind k, int slot, const SceneGeom& g) const {
+    return live(k, slot) && geom_[k][(size_t)slot].same(g);
+  }
 
   bool holds_any(int e) const { return dem_[(size_t)e] >= 0 || cm_[(size_t)e] >= 0 || Ke_[(size_t)e] != 0; }
   // Do the kernels get the table?  Only when an episode in use holds a slot or a K of its own.

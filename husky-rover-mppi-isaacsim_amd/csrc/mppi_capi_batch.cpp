@@ -12,6 +12,7 @@
 
 #include "mppi.h"
 #include "mppi_batch_scene.h"
+#include "mppi_batch_tasks.h"
 #include "mppi_ctx.h"
 #include "mppi_score.h"
 
@@ -48,6 +49,18 @@ struct mppi_batch {
   std::vector<Dem> dems;              // [kBatchMaxDems] a live slot owns its heights and normal table
   std::vector<DeviceBuf<float>> cms;  // [kBatchMaxCostmaps]
   DeviceBuf<BatchSceneTable> d_tab;   // the slots' pointer tables and the [E] records (BatchArgs::scene)
+  // the task queue (mppi_batch_set_tasks / _run_tasks): `tbook` decides, the rest is the list as given,
+  // the device's tables and the host's copy of the results
+  BatchTaskBook tbook;
+  std::vector<mppi_batch_task> tasks;
+  std::vector<BatchTaskResult> res;  // [N] as last read; a running task's is its lane's state
+  DeviceBuf<BatchTask> d_tasks;
+  DeviceBuf<BatchTaskResult> d_res;
+  DeviceBuf<BatchLane> d_lane;       // [E]
+  DeviceBuf<int> d_count;            // [1 + E] the next unclaimed task, then each lane's steps of the campaign
+  DeviceBuf<float> tlog;             // the log arena, [sum of max_steps][8]
+  std::vector<int> lane_steps;       // [E] as last read
+  enum Campaign { kNotStarted, kUnfinished, kComplete } campaign = kNotStarted;
 };
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
 static_assert(sizeof(SceneRecord) == sizeof(BatchScene), "SceneRecord is BatchScene field for field");
@@ -115,9 +128,12 @@ int slot_index(const mppi_batch* b, SceneKind k, int32_t slot) {
   return MPPI_OK;
 }
 
-// Free the slot unless an episode holds it.  (Its entry of the device table goes stale: no record names it.)
+// Free the slot unless an episode or a task of the list holds it.  (Its entry of the device table goes stale: no record names it.)
 int slot_free(mppi_batch* b, SceneKind k, int32_t slot) {
-  int who = -1;
+  int who = b->tbook.holder(k, slot);
+  if (who >= 0)
+    return fail(MPPI_EINVAL, std::string(k == kSceneDem ? "DEM" : "costmap") + " slot " + std::to_string(slot) +
+                                 " is held by task " + std::to_string(who) + " of the task list");
   if (b->book.free_slot(k, slot, &who) == kSceneSlotHeld)
     return fail(MPPI_EINVAL, std::string(k == kSceneDem ? "DEM" : "costmap") + " slot " + std::to_string(slot) +
                                  " is held by episode " + std::to_string(who));
@@ -174,6 +190,44 @@ int batch_pull(mppi_batch* b) {
   return MPPI_OK;
 }
 
+// The launches' scene and parameters; the kernels patch the episode's part.
+void step_args(mppi_ctx* c, const Plan& pl, RolloutArgs& a, FinishArgs& f) {
+  const mppi_state none{};
+  fill_rollout(c, pl, none, 0, nullptr, a);
+  a.clk = nullptr;
+  a.rec_m = nullptr;
+  a.ustore = nullptr;
+  a.inj_u1 = a.inj_u2 = nullptr;
+  a.k_offset = c->p.k_offset;
+  fill_finish(c, pl, none, f);
+  f.mode = 2;
+}
+
+// The batch's own part of the kernels' arguments: no variant table, no scene table and no log yet.
+BatchArgs batch_args(mppi_batch* b, int proj, const mppi_loop_policy& pol) {
+  const mppi_ctx* c = b->c;
+  BatchArgs z{};
+  z.ep_var = b->d_ep_var;
+  z.proj = proj;
+  z.ep = b->ep;
+  z.E = b->E;
+  z.blocks = b->blocks;
+  z.H = b->H;
+  z.k_pad = (int64_t)b->blocks * 256;
+  z.eps = b->eps;
+  z.unom = b->unom;
+  z.nodes = b->nodes;
+  z.cost = b->cost;
+  z.fin = b->fin;
+  z.sigma_base = pol.sigma_base;
+  z.sigma_div = pol.sigma_div;
+  z.goal_tol = pol.goal_tol;
+  z.horizon = c->p.horizon;
+  z.rwheel = c->p.robot_radius;
+  z.active_count = b->active_count;
+  return z;
+}
+
 int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol) {
   mppi_ctx* c = b->c;
   const Plan pl = make_plan(c);
@@ -215,37 +269,11 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
 
   RolloutArgs a;
   FinishArgs f;
-  const mppi_state none{};
-  fill_rollout(c, pl, none, 0, nullptr, a);  // scene and parameters; the kernel patches the episode's part
-  a.clk = nullptr;
-  a.rec_m = nullptr;
-  a.ustore = nullptr;
-  a.inj_u1 = a.inj_u2 = nullptr;
-  a.k_offset = c->p.k_offset;
-  fill_finish(c, pl, none, f);
-  f.mode = 2;
-  BatchArgs z{};
+  step_args(c, pl, a, f);
+  BatchArgs z = batch_args(b, proj, pol);
   z.var = any_var ? b->d_var : nullptr;  // null: the kernels of the batch without variants
-  z.ep_var = b->d_ep_var;
-  z.proj = proj;
-  z.ep = b->ep;
-  z.E = b->E;
-  z.blocks = b->blocks;
-  z.H = b->H;
-  z.k_pad = (int64_t)b->blocks * 256;
-  z.eps = b->eps;
-  z.unom = b->unom;
-  z.nodes = b->nodes;
-  z.cost = b->cost;
-  z.fin = b->fin;
   z.log = b->log;
   z.log_cap = b->log_cap;
-  z.sigma_base = pol.sigma_base;
-  z.sigma_div = pol.sigma_div;
-  z.goal_tol = pol.goal_tol;
-  z.horizon = c->p.horizon;
-  z.rwheel = c->p.robot_radius;
-  z.active_count = b->active_count;
   z.scene = b->book.need_table() ? b->d_tab.get() : nullptr;  // null: the kernels of the batch without scenes
   const int every = pol.check_every > 0 ? pol.check_every : 16;
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
@@ -267,6 +295,233 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
   b->last_ms = ms;
+  return MPPI_OK;
+}
+
+// ---- the task queue ----
+
+// An entry point that writes an episode's record or its row of the device's tables, while the
+// lanes of an unfinished campaign own them.
+int campaign_busy(const mppi_batch* b, const char* who) {
+  if (b->campaign != mppi_batch::kUnfinished) return MPPI_OK;
+  return fail(MPPI_ESTATE, std::string(who) + ": a campaign is unfinished (go on with mppi_batch_run_tasks, or "
+                                              "replace or clear the list with mppi_batch_set_tasks)");
+}
+
+// A campaign used the episodes as lanes.  The host puts its own per-episode variant indices and
+// scene records back on the device, and every episode is un-set (synchronous).
+int campaign_restore(mppi_batch* b) {
+  mppi_ctx* c = b->c;
+  const size_t E = (size_t)b->E;
+  std::vector<SceneRecord> recs(E);
+  for (size_t e = 0; e < E; ++e) recs[e] = b->book.record((int)e);
+  HIP_TRY(hipMemcpyAsync(b->d_ep_var, b->ep_var.data(), E * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_tab->rec, recs.data(), E * sizeof(BatchScene), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->ep, 0, E * sizeof(BatchEpisode), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // recs is pageable and dies here
+  b->host.assign(E, BatchEpisode{});
+  b->is_set.assign(E, 0);
+  b->book.mark_all_unset();
+  return MPPI_OK;
+}
+
+std::string task_error(const mppi_batch* b, int i, const mppi_batch_task& t, TaskError err, SceneKind kind) {
+  const std::string who = "task " + std::to_string(i) + ": ";
+  const int32_t s = kind == kSceneDem ? t.dem_slot : t.costmap_slot;
+  const std::string slot = std::string(kind == kSceneDem ? "dem_slot " : "costmap_slot ") + std::to_string(s);
+  switch (err) {
+    case kTaskVariant:
+      return who + "variant " + std::to_string(t.variant) + " outside the table of " +
+             std::to_string(b->variants.size()) + " rows";
+    case kTaskSlotRange:
+      return who + slot + " outside [-1, " + std::to_string(b->book.slots(kind)) + ")";
+    case kTaskSlotEmpty:
+      return who + slot + " is empty";
+    case kTaskSlotGeometry:
+      return who + slot + " was set with another geometry than the context's current " +
+             (kind == kSceneDem ? "DEM" : "costmap");
+    case kTaskKRange:
+      return who + "num_trajectories " + std::to_string(t.num_trajectories) + " outside [1, " +
+             std::to_string(b->c->p.num_trajectories) + "] (0: the context's)";
+    case kTaskMaxSteps:
+      return who + "max_steps " + std::to_string(t.max_steps) + " must be >= 1";
+    default:
+      return who + "the caps of the list sum to too many log rows";
+  }
+}
+
+void task_list_clear(mppi_batch* b) {
+  b->tbook.clear();
+  b->tasks.clear();
+  b->res.clear();
+  b->campaign = mppi_batch::kNotStarted;
+}
+
+BatchCampaign campaign_args(mppi_batch* b) {
+  BatchCampaign q{};
+  q.tasks = b->d_tasks;
+  q.res = b->d_res;
+  q.lane = b->d_lane;
+  q.next_task = b->d_count;
+  q.lane_steps = b->d_count + 1;
+  q.log = b->tlog;
+  q.ep_var = b->d_ep_var;
+  q.rec = b->d_tab->rec;
+  q.n = b->tbook.size();
+  return q;
+}
+
+// Results, lanes and step counters device -> host; a running task's result is its lane's state.
+int campaign_pull(mppi_batch* b) {
+  mppi_ctx* c = b->c;
+  const size_t E = (size_t)b->E, N = b->res.size();
+  std::vector<BatchLane> lanes(E);
+  std::vector<int> count(E + 1);
+  HIP_TRY(hipMemcpyAsync(b->res.data(), b->d_res, N * sizeof(BatchTaskResult), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(lanes.data(), b->d_lane, E * sizeof(BatchLane), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(count.data(), b->d_count, (E + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = batch_pull(b)) return rc;  // waits for the stream
+  b->lane_steps.assign(count.begin() + 1, count.end());
+  for (size_t e = 0; e < E; ++e) {
+    const BatchEpisode& r = b->host[e];
+    const int i = lanes[e].task;
+    if (!r.active || i < 0 || (size_t)i >= N) continue;
+    b->res[i] = BatchTaskResult{r.x0, r.y0, r.h0x, r.h0y, r.h0z, r.wl, r.wr, r.gx, r.gy, r.s1, r.s2, r.steps_run, 0, 1};
+  }
+  return MPPI_OK;
+}
+
+int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol, int32_t* tasks_done,
+                 int64_t* batch_steps) {
+  mppi_ctx* c = b->c;
+  const int N = b->tbook.size();
+  auto report = [&](int64_t steps) {
+    int done = 0;
+    for (const BatchTaskResult& r : b->res) done += (r.flags & 2) ? 1 : 0;
+    if (tasks_done) *tasks_done = done;
+    if (batch_steps) *batch_steps = steps;
+  };
+  b->last_ms = 0;
+  if (b->campaign == mppi_batch::kComplete) {
+    report(0);
+    return MPPI_OK;
+  }
+  const Plan pl = make_plan(c);
+  if (!pl.roles || pl.blocks != b->blocks)
+    return fail(MPPI_ESTATE, "batch: the context does not run the role-split rollout plan (MPPI_ROLES=0)");
+  RolloutArgs a;
+  FinishArgs f;
+  step_args(c, pl, a, f);
+  BatchArgs z = batch_args(b, proj, pol);
+  // the tables and the projections are decided from the list: the lanes' own rows change as they claim
+  z.var = b->tbook.need_variants() ? b->d_var.get() : nullptr;
+  z.scene = b->tbook.need_scene() ? b->d_tab.get() : nullptr;
+  std::vector<int> vproj(b->variants.size());
+  for (size_t i = 0; i < vproj.size(); ++i) vproj[i] = b->variants[i].proj;
+  bool use_proj[4];
+  b->tbook.projections(vproj, proj, use_proj);
+  const BatchCampaign q = campaign_args(b);
+  const size_t E = (size_t)b->E;
+  HIP_TRY(hipEventRecord(b->ev[0], c->stream));
+  if (b->campaign == mppi_batch::kNotStarted) {
+    // the first fill: every lane empty and counted active, then one claim each
+    HIP_TRY(hipMemsetAsync(b->ep, 0, E * sizeof(BatchEpisode), c->stream));
+    HIP_TRY(hipMemsetAsync(b->d_res, 0, (size_t)N * sizeof(BatchTaskResult), c->stream));
+    HIP_TRY(hipMemsetAsync(b->d_count, 0, (E + 1) * sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(b->d_lane, 0xff, E * sizeof(BatchLane), c->stream));
+    __atomic_store_n(b->active_count.get(), b->E, __ATOMIC_RELEASE);
+    b->lane_steps.assign(E, 0);
+    b->campaign = mppi_batch::kUnfinished;
+    HIP_TRY(launch_batch_claim(z, q, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  const int before = *std::max_element(b->lane_steps.begin(), b->lane_steps.end());
+  const int every = pol.check_every > 0 ? pol.check_every : 16;
+  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
+    const int m = std::min(every, n_steps - done);
+    for (int i = 0; i < m; ++i) {
+      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+      for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
+        if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
+      HIP_TRY(launch_batch_finish_campaign(f, z, q, pl.fin_lds_bytes, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    done += m;
+  }
+  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
+  HIP_TRY(hipEventSynchronize(b->ev[1]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+  b->last_ms = ms;
+  if (int rc = campaign_pull(b)) return rc;
+  report((int64_t)*std::max_element(b->lane_steps.begin(), b->lane_steps.end()) - before);
+  if (__atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) <= 0) {
+    b->campaign = mppi_batch::kComplete;
+    return campaign_restore(b);
+  }
+  return MPPI_OK;
+}
+
+// One launch of the log scorer over E paths of `log` (goals [E]; cmaps [E] or empty: every path on the
+// context's costmap; base_rows [E] or empty: path p begins at row p * stride), the results to the host.
+int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::vector<const float*>& cmaps,
+               const std::vector<int64_t>& base_rows, const float* log, const int32_t* lengths, int len_step,
+               int stride, const mppi_batch_variant* yardstick, mppi_path_scores* out, int32_t* rows,
+               const char* who) {
+  mppi_ctx* c = b->c;
+  const mppi_params& p = c->p;
+  const size_t E = goals.size();
+  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps][base rows]
+  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16, bp = up16(cmaps.size() * sizeof(float*)),
+               bb = base_rows.size() * sizeof(int64_t);
+  DeviceBuf<char> dbuf;
+  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp + bb));
+  char* buf = dbuf;
+  ScoreGoal* d_goals = (ScoreGoal*)buf;
+  float* d_cost = (float*)(buf + bg);
+  float* d_terms = (float*)(buf + bg + bn);
+  int32_t* d_col = (int32_t*)(buf + bg + bn + bt);
+  int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
+  const float** d_cmaps = (const float**)(buf + bg + bn + bt + bn + bn);
+  int64_t* d_base = (int64_t*)(buf + bg + bn + bt + bn + bn + bp);
+  ScoreArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.log = log;
+  a.goals = d_goals;
+  a.lengths = lengths;  // the device table's own counters, len_step ints apart
+  a.len_step = len_step;
+  a.rows_out = d_rows;
+  a.n = (int64_t)E;
+  a.stride = stride;
+  a.cm = c->cmap.cm;
+  a.cm_size = c->cmap.size;
+  a.hw = c->cmap.hw;
+  a.res_c = c->cmap.res;
+  a.vmax = p.v_max_linear;
+  a.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+  a.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+  a.w_path = yardstick ? yardstick->w_path : p.w_path;
+  a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+  a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+  a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  a.cost = d_cost;
+  a.terms = d_terms;
+  a.collisions = d_col;
+  a.cm_path = bp ? d_cmaps : nullptr;
+  a.base_row = bb ? d_base : nullptr;
+  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && bp)
+    e = hipMemcpyAsync(d_cmaps, cmaps.data(), cmaps.size() * sizeof(float*), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && bb) e = hipMemcpyAsync(d_base, base_rows.data(), bb, hipMemcpyHostToDevice, c->stream);
+  int rc = MPPI_OK;
+  if (e == hipSuccess) rc = run_score(c, a);
+  if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, E * 16, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == MPPI_OK && rows) e = hipMemcpyAsync(rows, d_rows, E * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string(who) + ": " + hipGetErrorString(e));
   return MPPI_OK;
 }
 
@@ -334,6 +589,7 @@ void mppi_batch_destroy(mppi_batch* b) {
 int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, uint64_t seed) {
   if (int rc = batch_episode(b, e)) return rc;
   if (!start) return fail(MPPI_EINVAL, "null argument");
+  if (int rc = campaign_busy(b, "batch_set_episode")) return rc;
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
@@ -375,6 +631,7 @@ int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (int rc = campaign_busy(b, "batch_run")) return rc;
   if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
   if (int rc_g = scene_geometry(b)) return rc_g;
@@ -479,6 +736,9 @@ int mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant* 
     if (b->ep_var[e] >= n)
       return fail(MPPI_EINVAL, "variants: episode " + std::to_string(e) + " holds row " +
                                    std::to_string(b->ep_var[e]) + " of the table, n = " + std::to_string(n));
+  if (const int i = b->tbook.variant_beyond(n); i >= 0)
+    return fail(MPPI_EINVAL, "variants: task " + std::to_string(i) + " of the task list holds row " +
+                                 std::to_string(b->tbook.task(i).variant) + " of the table, n = " + std::to_string(n));
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
@@ -497,6 +757,7 @@ int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
   if (variant < -1 || variant >= (int32_t)b->variants.size())
     return fail(MPPI_EINVAL, "variant index " + std::to_string(variant) + " outside the table of " +
                                  std::to_string(b->variants.size()) + " rows");
+  if (int rc = campaign_busy(b, "batch_set_episode_variant")) return rc;
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
@@ -577,6 +838,7 @@ int mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacle
 
 int mppi_batch_set_episode_scene(mppi_batch* b, int32_t e, int32_t dem_slot, int32_t costmap_slot) {
   if (int rc = batch_episode(b, e)) return rc;
+  if (int rc = campaign_busy(b, "batch_set_episode_scene")) return rc;
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   SceneKind bad = kSceneDem;
@@ -596,6 +858,7 @@ int mppi_batch_set_episode_scene(mppi_batch* b, int32_t e, int32_t dem_slot, int
 
 int mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_trajectories) {
   if (int rc = batch_episode(b, e)) return rc;
+  if (int rc = campaign_busy(b, "batch_set_episode_trajectories")) return rc;
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   const SceneRecord before = b->book.record(e);
@@ -653,53 +916,200 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
       cmaps[e] = s >= 0 ? b->cms[s].get() : c->cmap.cm.get();
     }
   }
-  // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps]
-  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16, bp = cmaps.size() * sizeof(float*);
-  DeviceBuf<char> dbuf;
-  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp));
-  char* buf = dbuf;
-  ScoreGoal* d_goals = (ScoreGoal*)buf;
-  float* d_cost = (float*)(buf + bg);
-  float* d_terms = (float*)(buf + bg + bn);
-  int32_t* d_col = (int32_t*)(buf + bg + bn + bt);
-  int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
-  const float** d_cmaps = (const float**)(buf + bg + bn + bt + bn + bn);
-  ScoreArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.log = b->log;
-  a.goals = d_goals;
-  a.lengths = &b->ep->steps_run;  // the episode table's own counters, one record apart
-  a.len_step = (int)(sizeof(BatchEpisode) / sizeof(int32_t));
-  a.rows_out = d_rows;
-  a.n = (int64_t)E;
-  a.stride = b->log_cap;
-  a.cm = c->cmap.cm;
-  a.cm_size = c->cmap.size;
-  a.hw = c->cmap.hw;
-  a.res_c = c->cmap.res;
-  a.vmax = p.v_max_linear;
-  a.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
-  a.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
-  a.w_path = yardstick ? yardstick->w_path : p.w_path;
-  a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
-  a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
-  a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
-  a.cost = d_cost;
-  a.terms = d_terms;
-  a.collisions = d_col;
-  a.cm_path = bp ? d_cmaps : nullptr;
-  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && bp) e = hipMemcpyAsync(d_cmaps, cmaps.data(), bp, hipMemcpyHostToDevice, c->stream);
-  int rc = MPPI_OK;
-  if (e == hipSuccess) rc = run_score(c, a);
-  if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, E * 16, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, E * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rc == MPPI_OK && rows) e = hipMemcpyAsync(rows, d_rows, E * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("batch_score: ") + hipGetErrorString(e));
+  return score_logs(b, goals, cmaps, {}, b->log, &b->ep->steps_run, (int)(sizeof(BatchEpisode) / sizeof(int32_t)),
+                    b->log_cap, yardstick, out, rows, "batch_score");
+}
+
+int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (n < 0) return fail(MPPI_EINVAL, "tasks: n must be >= 0");
+  if (n > 0 && !tasks) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<TaskSpec> specs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    specs[i].variant = tasks[i].variant;
+    specs[i].dem = tasks[i].dem_slot;
+    specs[i].cm = tasks[i].costmap_slot;
+    specs[i].K = tasks[i].num_trajectories;
+    specs[i].max_steps = tasks[i].max_steps;
+  }
+  BatchTaskBook fresh;
+  int bad = -1;
+  SceneKind kind = kSceneDem;
+  const TaskError err = fresh.set(specs, (int)b->variants.size(), b->book, dem_geom(c), costmap_geom(c),
+                                  c->p.num_trajectories, &bad, &kind);
+  if (err != kTaskOk) return fail(MPPI_EINVAL, task_error(b, bad, tasks[bad], err, kind));
+  // the list is replaced from here on: an unfinished campaign of the old one is abandoned
+  if (b->campaign == mppi_batch::kUnfinished)
+    if (int rc = campaign_restore(b)) return rc;
+  task_list_clear(b);
+  if (n == 0) return MPPI_OK;
+  const size_t N = (size_t)n, E = (size_t)b->E;
+  // the arena, and max_cap rows behind it: the scorer stages every path of a tile up to the tile's
+  // longest, so it reads (and drops) up to that many rows past a short last task
+  const size_t log_bytes = ((size_t)fresh.total_rows() + (size_t)fresh.max_cap()) * 8 * sizeof(float);
+  if (b->d_tasks.grow(N * sizeof(BatchTask)) || b->d_res.grow(N * sizeof(BatchTaskResult)) ||
+      b->d_lane.grow(E * sizeof(BatchLane)) || b->d_count.grow((E + 1) * sizeof(int)) || b->tlog.grow(log_bytes)) {
+    (void)hipGetLastError();
+    return fail(MPPI_EHIP, "tasks: allocation of the tables of " + std::to_string(n) + " tasks and a log arena of " +
+                               std::to_string(log_bytes) + " bytes failed");
+  }
+  std::vector<BatchTask> dev(N);
+  for (int i = 0; i < n; ++i) {
+    ServerCmd d;
+    state_fields(c->p, tasks[i].start, d);
+    BatchTask& t = dev[i];
+    t = BatchTask{};
+    t.x0 = d.x0;
+    t.y0 = d.y0;
+    t.h0x = d.h0x;
+    t.h0y = d.h0y;
+    t.h0z = d.h0z;
+    t.wl = d.wl;
+    t.wr = d.wr;
+    t.gx = d.gx;
+    t.gy = d.gy;
+    t.s1 = d.s1;
+    t.s2 = d.s2;
+    t.variant = tasks[i].variant;
+    t.seed = tasks[i].seed;
+    const SceneRecord r = fresh.record(i);
+    t.scene = BatchScene{r.dem, r.cm, r.K, r.blocks};
+    t.max_steps = tasks[i].max_steps;
+    t.log_base = fresh.base(i);
+  }
+  HIP_TRY(hipMemcpyAsync(b->d_tasks, dev.data(), N * sizeof(BatchTask), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->d_res, 0, N * sizeof(BatchTaskResult), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // dev is pageable and dies here
+  b->tbook = fresh;
+  b->tasks.assign(tasks, tasks + n);
+  b->res.assign(N, BatchTaskResult{});
   return MPPI_OK;
+}
+
+int mppi_batch_run_tasks(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop_policy* policy,
+                         int32_t* tasks_done, int64_t* batch_steps) {
+  if (!b || !policy) return fail(MPPI_EINVAL, "null argument");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  if (n_steps < 0) return fail(MPPI_EINVAL, "n_steps must be >= 0");
+  if (policy->check_every < 0) return fail(MPPI_EINVAL, "check_every must be >= 0");
+  if (!(policy->sigma_div != 0.0f)) return fail(MPPI_EINVAL, "sigma_div must be non-zero");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (b->tbook.empty()) return fail(MPPI_ESTATE, "batch_run_tasks: no task list: call mppi_batch_set_tasks first");
+  if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
+  if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
+  int s = b->tbook.mismatch(kSceneDem, b->book, dem_geom(c));
+  if (s >= 0)
+    return fail(MPPI_ESTATE, "batch_run_tasks: DEM slot " + std::to_string(s) +
+                                 " was set with another geometry than the context's current DEM");
+  s = b->tbook.mismatch(kSceneCostmap, b->book, costmap_geom(c));
+  if (s >= 0)
+    return fail(MPPI_ESTATE, "batch_run_tasks: costmap slot " + std::to_string(s) +
+                                 " was set with another geometry than the context's current costmap");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = campaign_run(b, proj, n_steps, *policy, tasks_done, batch_steps);
+  if (rc == MPPI_EHIP) b->failed = true;
+  return rc;
+}
+
+static int batch_task(mppi_batch* b, int32_t i) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (i < 0 || i >= b->tbook.size())
+    return fail(MPPI_EINVAL, "task index " + std::to_string(i) + " outside the list of " +
+                                 std::to_string(b->tbook.size()) + " tasks");
+  return MPPI_OK;
+}
+
+int mppi_batch_get_task(mppi_batch* b, int32_t i, mppi_state* state, int32_t* steps, int32_t* reached,
+                        int32_t* started) {
+  if (int rc = batch_task(b, i)) return rc;
+  const BatchTaskResult& r = b->res[i];  // the host's copy: mppi_batch_run_tasks read it back
+  if (state) {
+    if (r.flags == 0) {
+      *state = b->tasks[i].start;
+    } else {
+      state->x = r.x0;
+      state->y = r.y0;
+      state->heading[0] = r.h0x;
+      state->heading[1] = r.h0y;
+      state->heading[2] = r.h0z;
+      state->left_wheel_speed = r.wl;
+      state->right_wheel_speed = r.wr;
+      state->goal_x = r.gx;
+      state->goal_y = r.gy;
+      state->std_dev_u1 = r.s1;
+      state->std_dev_u2 = r.s2;
+    }
+  }
+  if (steps) *steps = r.steps;
+  if (reached) *reached = r.reached;
+  if (started) *started = (r.flags & 2) ? 2 : (r.flags & 1);
+  return MPPI_OK;
+}
+
+int mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t count, float* rows) {
+  if (int rc = batch_task(b, i)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "log range out of bounds");
+  if (count > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  if ((int64_t)first + count > b->res[i].steps)
+    return fail(MPPI_EINVAL, "task " + std::to_string(i) + ": log range beyond the " + std::to_string(b->res[i].steps) +
+                                 " steps the task has taken");
+  if (count == 0) return MPPI_OK;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(rows, b->tlog + ((size_t)b->tbook.base(i) + first) * 8, (size_t)count * 8 * sizeof(float),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                           mppi_path_scores* out, int32_t* rows) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!out) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (b->tbook.empty()) return fail(MPPI_ESTATE, "batch_score_tasks: no task list: call mppi_batch_set_tasks first");
+  if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score_tasks: no costmap: call mppi_set_costmap first");
+  const int s = b->tbook.mismatch(kSceneCostmap, b->book, costmap_geom(c));
+  if (s >= 0)
+    return fail(MPPI_ESTATE, "batch_score_tasks: costmap slot " + std::to_string(s) +
+                                 " was set with another geometry than the context's current costmap");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t N = (size_t)b->tbook.size();
+  std::vector<ScoreGoal> goals(N);
+  std::vector<int64_t> base(N);
+  for (size_t i = 0; i < N; ++i) {
+    const mppi_state& o = origins ? origins[i] : b->tasks[i].start;
+    mppi_state st{};
+    st.x = o.x;
+    st.y = o.y;
+    st.goal_x = o.goal_x;
+    st.goal_y = o.goal_y;
+    ServerCmd d;
+    state_fields(c->p, st, d);
+    goals[i] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
+    base[i] = b->tbook.base((int)i);
+  }
+  // each path on its task's costmap (no array at all while no listed task holds a costmap slot)
+  std::vector<const float*> cmaps;
+  if (b->tbook.any_costmap()) {
+    cmaps.resize(N);
+    for (size_t i = 0; i < N; ++i) {
+      const int cs = b->tbook.task((int)i).cm;
+      cmaps[i] = cs >= 0 ? b->cms[cs].get() : c->cmap.cm.get();
+    }
+  }
+  // lengths: the result table's own step counts (0 for a task that has not ended)
+  return score_logs(b, goals, cmaps, base, b->tlog, &b->d_res->steps, (int)(sizeof(BatchTaskResult) / sizeof(int32_t)),
+                    b->tbook.max_cap(), yardstick, out, rows, "batch_score_tasks");
 }
 
 }  // extern "C"

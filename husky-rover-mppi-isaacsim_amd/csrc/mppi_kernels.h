@@ -266,6 +266,51 @@ constexpr int kBatchMaxRecords = 16;  // leaf records per episode: the finish's 
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st);
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);
 hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st);
+// ---- the task queue of a batch (mppi_batch_set_tasks / _run_tasks) ----
+// The E episodes become lanes that work through N tasks: the lane whose task ends (goal reached, or
+// the task's step cap) writes the task's result and claims the next index of the list with one
+// agent-scope atomic add, in the finish kernel's campaign form.  The other kernels do not know:
+// they read the lane's BatchEpisode, ep_var[e] and scene->rec[e], which the finish rewrote behind
+// a kernel boundary.
+struct BatchTask {  // one task as the host resolved it (mppi_batch_task)
+  float x0, y0, h0x, h0y, h0z, wl, wr, gx, gy, s1, s2;  // the start, heading as given
+  int variant;          // row of the variant table, -1: none
+  uint64_t seed;        // Philox key
+  BatchScene scene;     // slots (-1: the context's), K and blocks, resolved
+  int max_steps;        // >= 1
+  int pad;
+  int64_t log_base;     // first row of the task in the log arena: the prefix sum of the caps before it
+};
+static_assert(sizeof(BatchTask) == 88, "BatchTask layout");
+struct BatchTaskResult {
+  float x0, y0, h0x, h0y, h0z, wl, wr, gx, gy, s1, s2;  // the state after the task's last step
+  int steps;    // steps taken = rows of the task in the arena
+  int reached;  // the goal test passed
+  int flags;    // 1: claimed by a lane, 2: ended
+};
+static_assert(sizeof(BatchTaskResult) == 56, "BatchTaskResult layout");
+struct BatchLane {  // what a lane keeps of its task beside its BatchEpisode: one 16-byte load
+  int task;         // index into the list, -1: none
+  int max_steps;
+  int64_t log_base;
+};
+static_assert(sizeof(BatchLane) == 16, "BatchLane layout");
+struct BatchCampaign {
+  const BatchTask* tasks;  // [n]
+  BatchTaskResult* res;    // [n]
+  BatchLane* lane;         // [E]
+  int* next_task;          // the next unclaimed index (may pass n by the number of lanes)
+  int* lane_steps;         // [E] the steps each lane has run: lanes run without gaps until the list is
+                           // exhausted, so the largest is the campaign's batch steps so far
+  float* log;              // [sum of max_steps][8] the arena
+  int* ep_var;             // [E] BatchArgs::ep_var, writable
+  BatchScene* rec;         // [E] BatchSceneTable::rec, writable
+  int n;
+};
+// The first fill: E workgroups claim as a finishing lane does (one statement of the rule).
+hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st);
+hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
+                                        hipStream_t st);
 
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);

@@ -56,6 +56,10 @@ struct ScoreArgs {
   // with `log` only: [n] each path's own costmap of cm's geometry (device pointers; an episode's
   // costmap slot, mppi_batch_score), or null: every path on cm
   const float* const* cm_path;
+  // with `log` only: [n] the first row of each path in the log (device memory, rows >= 0: the task
+  // logs of a batch, an arena of paths of different capacities; mppi_batch_score_tasks), or null:
+  // path p begins at row p * stride.  With base rows `stride` only bounds the lengths.
+  const int64_t* base_row;
 };
 
 hipError_t launch_score(const ScoreArgs& a, hipStream_t st);

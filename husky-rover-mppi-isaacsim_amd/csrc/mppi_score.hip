@@ -104,8 +104,9 @@ struct StageLog {
   float q[LOG_WP][4];
 };
 
-// Waypoint u of the tile = row t0 + u % len of path p0 + u / len.
-template <bool STORE>
+// Waypoint u of the tile = row t0 + u % len of path p0 + u / len.  RAGGED: path p begins at row
+// base_row[p] of the log (an arena of paths of different capacities) instead of p * stride.
+template <bool STORE, bool RAGGED>
 __device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
                                                 int tid) {
   const bool full = len == CT;
@@ -118,7 +119,11 @@ __device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r,
     const int tt = u - pp * len;
     if (p0 + pp >= a.n) continue;
     if constexpr (!STORE) {
-      const float* src = a.log + ((size_t)(p0 + pp) * (size_t)a.stride + (size_t)(t0 + tt)) * 8;
+      const float* src;
+      if constexpr (RAGGED)
+        src = a.log + ((size_t)a.base_row[p0 + pp] + (size_t)(t0 + tt)) * 8;
+      else
+        src = a.log + ((size_t)(p0 + pp) * (size_t)a.stride + (size_t)(t0 + tt)) * 8;
       const float4 xyz = *reinterpret_cast<const float4*>(src);
       r.q[i][0] = xyz.x;
       r.q[i][1] = xyz.y;
@@ -134,13 +139,13 @@ __device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r,
   }
 }
 
-template <int VEC, bool WHEELS, bool STORE>
+template <int VEC, bool WHEELS, bool STORE, bool RAGGED>
 __device__ __forceinline__ void stage_chunk(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
                                             int tid) {
-  stage_chunk_log<STORE>(a, r, sm, p0, t0, len, tid);
+  stage_chunk_log<STORE, RAGGED>(a, r, sm, p0, t0, len, tid);
 }
 
-template <int VEC, bool WHEELS, bool STORE>
+template <int VEC, bool WHEELS, bool STORE, bool RAGGED>
 __device__ __forceinline__ void stage_chunk(const ScoreArgs& a, Stage<VEC>& r, Smem& sm, int64_t p0, int t0, int len,
                                             int tid) {
   stage_array<VEC, 3, stage_floats(3, VEC), STORE>(a.traj, r.a[0], sm.a[0], ROW3, p0, a.n, a.stride, t0, len, tid);
@@ -173,9 +178,11 @@ __device__ __forceinline__ int cm_index(const ScoreArgs& a, float x, float y) {
 }
 
 // LOG: the paths are a batch's log with per-path goal terms (see above); VEC = 1, WHEELS = false there.
-template <int VEC, bool WHEELS, bool LOG = false>
+// RAGGED (mppi_batch_score_tasks): the LOG loader with a base row per path (ScoreArgs::base_row).
+template <int VEC, bool WHEELS, bool LOG = false, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
   static_assert(!LOG || (VEC == 1 && !WHEELS), "the log loader takes whole rows and has no wheel arrays");
+  static_assert(!RAGGED || LOG, "base rows belong to the log loader");
   __shared__ Smem sm;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -223,14 +230,14 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
   }
 
   std::conditional_t<LOG, StageLog, Stage<VEC>> r;
-  stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, 0, min(CT, Lld), tid);
-  stage_chunk<VEC, WHEELS, true>(a, r, sm, p0, 0, min(CT, Lld), tid);
+  stage_chunk<VEC, WHEELS, false, RAGGED>(a, r, sm, p0, 0, min(CT, Lld), tid);
+  stage_chunk<VEC, WHEELS, true, RAGGED>(a, r, sm, p0, 0, min(CT, Lld), tid);
   __syncthreads();
   for (int t0 = 0; t0 < Lld; t0 += CT) {
     const int len = min(CT, Lld - t0);
     const int t1 = t0 + CT;
     const int len1 = min(CT, Lld - t1);  // <= 0: no next chunk
-    if (len1 > 0) stage_chunk<VEC, WHEELS, false>(a, r, sm, p0, t1, len1, tid);
+    if (len1 > 0) stage_chunk<VEC, WHEELS, false, RAGGED>(a, r, sm, p0, t1, len1, tid);
 
     const int te = min(t0 + len, L);  // this lane's waypoints of the chunk: [t0, te)
     if (role == 0) {
@@ -294,7 +301,7 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     }
     __syncthreads();  // every wave is done with the staged chunk
     if (len1 > 0) {
-      stage_chunk<VEC, WHEELS, true>(a, r, sm, p0, t1, len1, tid);
+      stage_chunk<VEC, WHEELS, true, RAGGED>(a, r, sm, p0, t1, len1, tid);
       __syncthreads();
     }
   }
@@ -330,9 +337,13 @@ hipError_t launch_score(const ScoreArgs& a, hipStream_t st) {
     // stride 0: no run yet, every length is clamped to 0 and no row is read
     if (!a.goals || !a.lengths || !a.cm || a.lw || a.rw || a.stride < 0 || a.cm_size < 1 || a.len_step < 1 ||
         ((uintptr_t)a.log & 31) != 0 || (a.terms && !aligned16(a.terms)) ||
-        a.n * (int64_t)std::max(a.stride, 1) >= ((int64_t)1 << 31))
+        (!a.base_row && a.n * (int64_t)std::max(a.stride, 1) >= ((int64_t)1 << 31)))
       return hipErrorInvalidValue;
-    hipLaunchKernelGGL((mppi_score_kernel<1, false, true>), dim3((unsigned)((a.n + TP - 1) / TP)), dim3(NT), 0, st, a);
+    const dim3 grid((unsigned)((a.n + TP - 1) / TP));
+    if (a.base_row)
+      hipLaunchKernelGGL((mppi_score_kernel<1, false, true, true>), grid, dim3(NT), 0, st, a);
+    else
+      hipLaunchKernelGGL((mppi_score_kernel<1, false, true>), grid, dim3(NT), 0, st, a);
     return hipGetLastError();
   }
   if (!a.traj || !a.v || !a.cm || a.stride < 1 || a.cm_size < 1 || (a.lw == nullptr) != (a.rw == nullptr) ||

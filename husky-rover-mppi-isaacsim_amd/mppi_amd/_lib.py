@@ -82,6 +82,12 @@ class MppiBatchVariant(C.Structure):
     _fields_ = [(n, C.c_float) for n in VARIANT_FIELDS] + [("proj", C.c_int32)]
 
 
+class MppiBatchTask(C.Structure):
+    """mppi_batch_task: one task of a batch's task list (88 bytes)."""
+    _fields_ = [("start", MppiState), ("seed", C.c_uint64), ("variant", C.c_int32), ("dem_slot", C.c_int32),
+                ("costmap_slot", C.c_int32), ("num_trajectories", C.c_int64), ("max_steps", C.c_int32)]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
 
 
@@ -166,6 +172,14 @@ _PROTOS = {
     "mppi_batch_set_episode_trajectories": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "mppi_batch_score": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
                                    C.POINTER(MppiPathScores), C.POINTER(C.c_int32)]),
+    "mppi_batch_set_tasks": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchTask)]),
+    "mppi_batch_run_tasks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MppiLoopPolicy),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "mppi_batch_get_task": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiState), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mppi_batch_get_task_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_score_tasks": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
+                                         C.POINTER(MppiPathScores), C.POINTER(C.c_int32)]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
                                          C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_int32)]),
 }
@@ -678,6 +692,17 @@ def _as_variant(v):
     return v if isinstance(v, MppiBatchVariant) else make_variant(**dict(v))
 
 
+def make_task(start, seed, max_steps, variant=-1, dem=-1, costmap=-1, trajectories=0):
+    """Fill mppi_batch_task: what Batch.set_episode takes (start: MppiState, the heading used as
+    given), plus the step cap."""
+    t = MppiBatchTask()
+    t.start = start
+    t.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    t.variant, t.dem_slot, t.costmap_slot = int(variant), int(dem), int(costmap)
+    t.num_trajectories, t.max_steps = int(trajectories), int(max_steps)
+    return t
+
+
 class Batch:
     """mppi_batch (include/mppi.h): E closed-loop episodes over one Engine's scene and parameters,
     advanced on the GPU with no host work between steps.  Keeps a reference to its Engine, so the
@@ -804,6 +829,61 @@ class Batch:
         _check(self.lib, self.lib.mppi_batch_get_log(self.h, int(e), int(first), int(count), _fp(rows)),
                "mppi_batch_get_log")
         return rows
+
+    # ---- the task queue: N tasks on the E episodes as lanes (mppi_batch_set_tasks / _run_tasks) ----
+    def set_tasks(self, tasks):
+        """The batch's task list: MppiBatchTask (make_task) or dicts of make_task's arguments; an empty
+        list clears it.  The results are reset."""
+        rows = [t if isinstance(t, MppiBatchTask) else make_task(**dict(t)) for t in tasks]
+        arr = (MppiBatchTask * max(len(rows), 1))(*rows)
+        _check(self.lib, self.lib.mppi_batch_set_tasks(self.h, len(rows), arr), "mppi_batch_set_tasks")
+        self.n_tasks = len(rows)
+
+    def run_tasks(self, n_steps, proj="3d", policy=None):
+        """Advance the campaign by up to n_steps batch steps (it stops when every task has ended; a
+        further call goes on).  Returns (tasks ended so far, batch steps of this call)."""
+        pol = policy if policy is not None else make_policy()
+        done, steps = C.c_int32(), C.c_int64()
+        _check(self.lib, self.lib.mppi_batch_run_tasks(self.h, PROJ[proj], int(n_steps), C.byref(pol), C.byref(done),
+                                                       C.byref(steps)), "mppi_batch_run_tasks")
+        return done.value, steps.value
+
+    def task(self, i):
+        """dict(state (MppiState), steps, reached, started: 0 not yet claimed, 1 running, 2 ended)."""
+        st = MppiState()
+        steps, reached, started = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(self.lib, self.lib.mppi_batch_get_task(self.h, int(i), C.byref(st), C.byref(steps), C.byref(reached),
+                                                      C.byref(started)), "mppi_batch_get_task")
+        return dict(state=st, steps=steps.value, reached=bool(reached.value), started=started.value)
+
+    def task_log(self, i, first=0, count=None):
+        """Rows [count, 8] of task i: x, y, z, the normalised heading, v, w per step."""
+        if count is None:
+            count = self.task(i)["steps"] - int(first)
+        rows = np.zeros((max(int(count), 0), 8), np.float32)
+        _check(self.lib, self.lib.mppi_batch_get_task_log(self.h, int(i), int(first), int(count), _fp(rows)),
+               "mppi_batch_get_task_log")
+        return rows
+
+    def score_tasks(self, yardstick=None, origins=None):
+        """mppi_batch_score_tasks: score() over the N task logs, each on its task's costmap; origins: N
+        MppiState (default each task's start and goal).  Returns dict(cost [N], terms [N, 4],
+        collisions [N], rows [N])."""
+        N = int(getattr(self, "n_tasks", 0))
+        out = dict(cost=np.zeros(N, np.float32), terms=np.zeros((N, 4), np.float32),
+                   collisions=np.zeros(N, np.int32), rows=np.zeros(N, np.int32))
+        i32 = C.POINTER(C.c_int32)
+        sc = MppiPathScores(_fp(out["cost"]), _fp(out["terms"]), out["collisions"].ctypes.data_as(i32))
+        y = None if yardstick is None else C.byref(_as_variant(yardstick))
+        o = None
+        if origins is not None:
+            origins = list(origins)
+            if len(origins) != N:
+                raise ValueError(f"{N} tasks but {len(origins)} origins")
+            o = (MppiState * max(N, 1))(*origins)
+        _check(self.lib, self.lib.mppi_batch_score_tasks(self.h, y, o, C.byref(sc), out["rows"].ctypes.data_as(i32)),
+               "mppi_batch_score_tasks")
+        return out
 
     def last_ms(self):
         ms = C.c_double()

@@ -112,6 +112,70 @@ def episode_scenes(E, K, dems=None, costmaps=None, episode_dem=None, episode_cos
     return ed, ec, ek
 
 
+def campaign_tasks(N, K, max_loops, variants=None, dems=None, costmaps=None, task_variant=None, task_dem=None,
+                   task_costmap=None, task_trajectories=None):
+    """The per-task arguments of MPPI_Controller.run_campaign, checked and filled in:
+    ([variant row] * N, [dem slot] * N, [costmap slot] * N, [K_i] * N, [max_steps] * N), with
+    -1 / -1 / -1 / 0 for the controller's own.
+
+    The checks of episode_scenes with tasks in place of episodes, and: task_variant[i] an index into
+    `variants` (-1 or None: none); max_loops one step cap >= 1 for every task, or N of them.
+    ValueError names the argument and the task.
+    """
+    N = int(N)
+    if N < 1:
+        raise ValueError("a campaign needs at least one task")
+    try:
+        ed, ec, ek = episode_scenes(N, K, dems, costmaps, task_dem, task_costmap, task_trajectories)
+    except ValueError as err:
+        raise ValueError(str(err).replace("episode_", "task_").replace("episodes", "tasks")) from None
+    nv = 0 if variants is None else len(variants)
+    tv = [-1] * N if task_variant is None else [-1 if v is None else int(v) for v in task_variant]
+    if len(tv) != N:
+        raise ValueError(f"{N} tasks but {len(tv)} entries in task_variant")
+    if any(v >= 0 for v in tv) and nv == 0:
+        raise ValueError("task_variant names rows of `variants`, which is empty")
+    for i, v in enumerate(tv):
+        if v < -1 or v >= nv:
+            raise ValueError(f"task_variant[{i}] = {v} outside the {nv} rows of `variants`")
+    caps = [int(max_loops)] * N if np.ndim(max_loops) == 0 else [int(m) for m in max_loops]
+    if len(caps) != N:
+        raise ValueError(f"{N} tasks but {len(caps)} entries in max_loops")
+    for i, m in enumerate(caps):
+        if m < 1:
+            raise ValueError(f"max_loops[{i}] = {m}: a task's step cap must be >= 1")
+    return tv, ed, ec, ek, caps
+
+
+def campaign_makespan(lengths, lanes):
+    """The batch steps a campaign needs for tasks that take `lengths` steps on `lanes` lanes: the
+    device's claim rule, greedy list scheduling in list order.  A free lane takes the next task of
+    the list in the same step; a task of length 0 (its start inside the goal tolerance) is consumed
+    without a step.  Plain Python."""
+    lanes = int(lanes)
+    if lanes < 1:
+        raise ValueError("lanes must be >= 1")
+    todo = [int(n) for n in lengths]
+    if any(n < 0 for n in todo):
+        raise ValueError("lengths must be >= 0")
+    todo.reverse()
+    busy = []          # steps left of each running lane
+
+    def fill():
+        while len(busy) < lanes and todo:
+            n = todo.pop()
+            if n > 0:
+                busy.append(n)
+
+    fill()
+    steps = 0
+    while busy:
+        steps += 1
+        busy[:] = [n - 1 for n in busy if n > 1]
+        fill()
+    return steps
+
+
 def normalise_heading(hv):
     """Row 0 of heading_sim widened to float64 and divided by sqrt((h0 h0 + h1 h1) + h2 h2) (the sum
     left to right, every operation rounded once), each component rounded to float32."""

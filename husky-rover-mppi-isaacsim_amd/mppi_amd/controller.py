@@ -18,7 +18,7 @@ import numpy as np
 import yaml
 
 from . import _lib, scene
-from .batch import episode_scenes
+from .batch import campaign_tasks, episode_scenes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CONFIG = os.path.join(_HERE, "config.yaml")
@@ -562,6 +562,66 @@ class MPPI_Controller:
             if score is None or score is False:
                 return out
             return out, batch.score(None if score is True else score)
+        finally:
+            batch.close()
+
+    def run_campaign(self, starts, headings, goals, seeds=None, lanes=64, max_loops=None, proj="3d", policy=None,
+                     variants=None, task_variant=None, score=None, dems=None, costmaps=None, task_dem=None,
+                     task_costmap=None, task_trajectories=None):
+        """run_batch for N tasks on `lanes` episodes (mppi_batch_set_tasks / _run_tasks):
+        the lane whose task ends (goal reached, or its step cap) takes the next task of the list on the
+        GPU in the same step, so a campaign of runs of very different lengths keeps every lane busy
+        and costs no host work between its runs.  Every task's trail is the one run_batch gives the
+        same start, goal, seed, variant, scene and trajectory count as an episode.
+
+        starts / headings / goals / seeds / proj / policy / variants / dems / costmaps / score: as
+        run_batch, per task.  max_loops: one step cap for every task (default the controller's) or
+        one per task.  task_variant / task_dem / task_costmap / task_trajectories: run_batch's
+        episode_* arguments, per task.  lanes: the episodes the campaign runs on (at most the tasks).
+
+        Returns what run_batch returns, one dict per task (with `score` the pair).
+        """
+        starts = np.asarray(starts, np.float64).reshape(-1, 2)
+        N = starts.shape[0]
+        headings = np.asarray(headings, np.float64).reshape(N, 3)
+        goals = np.asarray(goals, np.float64).reshape(N, 2)
+        seeds = [self.seed + i for i in range(N)] if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != N:
+            raise ValueError(f"{N} tasks but {len(seeds)} seeds")
+        tv, td, tc, tk, caps = campaign_tasks(N, self.number_of_trajectories,
+                                              self.max_loops if max_loops is None else max_loops, variants, dems,
+                                              costmaps, task_variant, task_dem, task_costmap, task_trajectories)
+        if int(lanes) < 1:
+            raise ValueError("lanes must be >= 1")
+        if self.engine is None:
+            self.warp_setup()
+        pol = _lib.make_policy(**(policy or {}))
+        batch = _lib.Batch(self.engine, min(int(lanes), N))
+        try:
+            if variants:
+                batch.set_variants(variants)
+            for slot, Z in enumerate(dems or []):
+                Z = np.asarray(Z, np.float32)
+                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
+            for slot, cm in enumerate(costmaps or []):
+                self._fill_costmap_slot(batch, slot, cm)
+            batch.set_tasks([_lib.make_task(_lib.make_state(starts[i, 0], starts[i, 1], headings[i], 0.0, 0.0,
+                                                            goals[i, 0], goals[i, 1], self.std_dev_u1,
+                                                            self.std_dev_u2),
+                                            seeds[i], caps[i], tv[i], td[i], tc[i], tk[i]) for i in range(N)])
+            done = 0
+            while done < N:     # every task ends within its cap, so the campaign ends
+                done, _ = batch.run_tasks(max(caps), proj, pol)
+            out = []
+            for i in range(N):
+                info = batch.task(i)
+                rows = batch.task_log(i, 0, info["steps"])
+                out.append(dict(x=[starts[i, 0]] + list(rows[:, 0]), y=[starts[i, 1]] + list(rows[:, 1]),
+                                z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
+                                loops=info["steps"], reached=info["reached"]))
+            if score is None or score is False:
+                return out
+            return out, batch.score_tasks(None if score is True else score)
         finally:
             batch.close()
 

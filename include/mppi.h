@@ -435,6 +435,60 @@ int  mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_t
 int  mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
                       mppi_path_scores* out, int32_t* rows);
 
+/* ---- a batch's task queue: N tasks on the batch's E episodes as lanes ----
+ * A campaign is many runs of very different lengths (goal reached early, a detour, the step cap).
+ * Run as plain batches, every episode that has ended idles until the slowest one of its batch ends,
+ * and every batch costs E mppi_batch_set_episode calls and readbacks.  With a task list the lane
+ * whose task ends takes the next task of the list itself, on the device, in the same step, until
+ * the list is empty: no host work and no idle lane in between.
+ * Contract, per task: every step is bitwise the mppi_step of a context with that task's seed, state,
+ * step index (from 0), variant, DEM, costmap and num_trajectories, exactly as for an episode given
+ * the same through the per-episode setters.  Which lane runs which task shows in no result.
+ * A task whose start lies inside the goal tolerance takes no step: steps = 0, reached = 1. */
+typedef struct mppi_batch_task {         /* 88 bytes */
+  mppi_state start;                      /* the heading used as given */
+  uint64_t   seed;                       /* Philox key */
+  int32_t    variant;                    /* row of the batch's variant table, -1: none */
+  int32_t    dem_slot, costmap_slot;     /* -1: the context's */
+  int64_t    num_trajectories;           /* in [1, context K], 0: the context's */
+  int32_t    max_steps;                  /* >= 1: the task ends unreached after this many steps */
+} mppi_batch_task;
+/* The batch's task list: n >= 1 tasks, copied to device memory, the results reset; n = 0 clears the
+ * list.  Every task is checked by the rules of the per-episode setters (variant index inside the
+ * table; slots live and of the context's current geometry; num_trajectories in [1, context K] or 0;
+ * max_steps >= 1): MPPI_EINVAL names the task and the field, and the list stays as it was.  The log
+ * arena of sum(max_steps) rows of 32 bytes is allocated here: MPPI_EHIP with the size when that
+ * fails (the list is then empty).  While a list stands, a slot one of its tasks holds is not freed
+ * and the variant table is not shortened below a row one of them names (MPPI_EINVAL, naming the
+ * task).  Replacing or clearing the list of an unfinished campaign abandons it. */
+int  mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks);
+/* Advances the campaign by up to n_steps batch steps in chunks of policy->check_every, as
+ * mppi_batch_run does, and stops early when every task has ended; a further call continues where
+ * this one stopped.  The first call of a list fills the lanes (one claim launch).  proj and the
+ * policy's sigma schedule apply to tasks without a variant, as for episodes; every call of one
+ * campaign should pass the same.  tasks_done (may be NULL): tasks ended so far; batch_steps (may be
+ * NULL): the batch steps of this call.  MPPI_ESTATE without a list, without a DEM and costmap, when
+ * a listed slot no longer has the context's geometry, or after a HIP error of the batch.  When
+ * every task has ended the call returns at once.
+ * The episodes are the lanes: a campaign overwrites their states.  While a campaign is unfinished
+ * mppi_batch_run answers MPPI_ESTATE.  When the campaign completes, or its list is replaced or
+ * cleared, the episodes' own variant indices, scenes and trajectory counts are as before the
+ * campaign, and every episode is un-set: not runnable until mppi_batch_set_episode. */
+int  mppi_batch_run_tasks(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop_policy* policy,
+                          int32_t* tasks_done, int64_t* batch_steps);
+/* Task i's result (any output may be NULL): the state after its last step so far, the steps taken,
+ * whether the goal test passed, and started = 0 (not yet claimed by a lane), 1 (running), 2 (ended). */
+int  mppi_batch_get_task(mppi_batch* b, int32_t i, mppi_state* state, int32_t* steps, int32_t* reached,
+                         int32_t* started);
+/* Rows [first, first + count) of task i's log (8 floats each, as mppi_batch_get_log); MPPI_EINVAL
+ * beyond the steps the task has taken. */
+int  mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t count, float* rows);
+/* mppi_batch_score over the N task logs: each path on its task's costmap (its slot's, or the
+ * context's).  origins: NULL or [N]; NULL = each task's start and goal.  out: arrays of N; rows [N].
+ * A task that has not ended scores as a path without rows. */
+int  mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                            mppi_path_scores* out, int32_t* rows);
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

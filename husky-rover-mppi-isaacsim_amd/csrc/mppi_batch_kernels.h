@@ -11,6 +11,10 @@
 // The task queue (mppi_batch_run_tasks): the finish kernel's campaign form lets the lane whose task
 // ended claim the next task of a list in device memory (campaign_claim / campaign_refill); the one
 // word two workgroups of a launch share is the list's counter, taken with an agent-scope atomic add.
+//
+// The device-resident step (mppi_batch_step_device): mppi_batch_ingest_kernel writes states held in
+// device memory into the records ahead of the noise launch, and the finish kernel's step form hands
+// the command and the plan out instead of advancing.  The noise and rollout kernels are the same.
 #pragma once
 
 // The normals of every active episode's current step, [blocks][2][H][256] per episode, addressed as
@@ -102,6 +106,21 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
   roles_body<256, PROJ, 0, false, false>(a, (int)blockIdx.x, nullptr);
 }
 
+// The critics' scalar parts of an episode at (x, y) with the goal (gx, gy): state_fields() of
+// mppi_capi.cpp, the same float32 operations in the same order (IEEE sqrtf and /).  The one statement
+// of the rule on the device: the claim, the advance lane and the ingest all write them through this.
+__device__ __forceinline__ void episode_goal_fields(BatchEpisode* ep, float x, float y, float gx, float gy,
+                                                    float horizon) {
+  const float xd = gx - x;
+  const float yd = gy - y;
+  const float dist = sqrtf(xd * xd + yd * yd);
+  ep->pf_far = dist > horizon ? 1 : 0;
+  ep->igx = x + (xd * horizon) / (dist + 1e-6f);
+  ep->igy = y + (yd * horizon) / (dist + 1e-6f);
+  ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
+  ep->speed_on = (dist < 2.0f) ? 0 : 1;
+}
+
 // The claim rule of the task queue, run by one thread of lane e whose task is over (or that has
 // none yet: the first fill).  Takes the next index of the list with one agent-scope atomic add; a
 // task whose start already passes the goal test takes no step: its result is written at once
@@ -151,17 +170,7 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
     ep->gy = gy;
     ep->s1 = t->s1;
     ep->s2 = t->s2;
-    {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
-      const float xd = gx - x;
-      const float yd = gy - y;
-      const float dist = sqrtf(xd * xd + yd * yd);
-      const float horizon = b.horizon;
-      ep->pf_far = dist > horizon ? 1 : 0;
-      ep->igx = x + (xd * horizon) / (dist + 1e-6f);
-      ep->igy = y + (yd * horizon) / (dist + 1e-6f);
-      ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
-      ep->speed_on = (dist < 2.0f) ? 0 : 1;
-    }
+    episode_goal_fields(ep, x, y, gx, gy, b.horizon);
     ep->active = 1;
     ep->cur = 0;
     ep->seed = t->seed;
@@ -204,13 +213,25 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // refills the lane (campaign_refill above) instead of going inactive.  The campaign form is the
 // instantiation with the queue as its own third kernel argument; the plain form takes the two
 // arguments it always took (BatchArgs does not grow).
+//
+// STEP (mppi_batch_step_device): the plant is the caller's.  Instead of the advance one lane writes
+// the command (v, w) to io.cmd[e], flips the nominal double buffer and counts the step, and the
+// workgroup copies the 4H + 12 outputs to io.plan[e]: no advance rule, no goal test, no log row, no
+// touch of the active count.  The state stays what the ingest kernel (below) wrote.  The io pointers
+// are this form's own third kernel argument, as the queue is the campaign form's.
 __device__ __forceinline__ const BatchCampaign* queue_of() { return nullptr; }
 __device__ __forceinline__ const BatchCampaign* queue_of(const BatchCampaign& q) { return &q; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchIo&) { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of() { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchCampaign&) { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchIo& io) { return &io; }
 template <class... Queue>
 __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
                                                                          const Queue... queue) {
-  static_assert(sizeof...(Queue) <= 1, "at most the one queue");
-  constexpr bool CAMPAIGN = sizeof...(Queue) == 1;
+  static_assert(sizeof...(Queue) <= 1, "at most the one queue, or the one io block");
+  constexpr bool CAMPAIGN = (std::is_same<Queue, BatchCampaign>::value || ...);
+  constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...);
+  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP ? 1 : 0), "the third argument is a BatchCampaign or a BatchIo");
   const BatchCampaign* q = queue_of(queue...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int e = blockIdx.x;
@@ -297,6 +318,28 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   const float ures = (tid < 2 * H && S > 0.0) ? (float)(lnode[2 + tid] / S) : 0.0f;
   __syncthreads();  // lnode is dead from here on
   finish_phase2(f, ures, smem_raw, tid, FIN_THREADS);
+  if constexpr (STEP) {
+    // ---------------- (3') the command and the plan out (after finish_phase2's closing barrier; its
+    // outputs were written through, so agent-scope loads see them)
+    const BatchIo* io = io_of(queue...);
+    auto ld = [&](int i) __attribute__((always_inline)) {
+      return __hip_atomic_load(f.out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    const int nplan = 4 * H + 12;
+    if (io->plan) {
+      float* plan = io->plan + (size_t)e * nplan;
+      for (int j = tid; j < nplan; j += FIN_THREADS) plan[j] = ld(j);
+    }
+    if (tid == 0) {
+      if (io->cmd) {
+        io->cmd[2 * (size_t)e] = ld(2 * H);
+        io->cmd[2 * (size_t)e + 1] = ld(3 * H);
+      }
+      ep->cur = cur_buf ^ 1;
+      ep->step = ep->step + 1;
+    }
+    return;
+  }
   // ---------------- (3) advance (finish_phase2 ends with every output store complete and a barrier;
   // the outputs were written through, so agent-scope loads see them)
   if constexpr (!CAMPAIGN) {
@@ -336,17 +379,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     ep->wr = v + half;
     ep->s1 = fmaxf(sigma_base, sigma_base - ww);
     ep->s2 = fmaxf(sigma_base, sigma_base + ww);
-    {  // state_fields() of mppi_capi.cpp: the same float32 operations in the same order
-      const float xd = gx - x;
-      const float yd = gy - y;
-      const float dist = sqrtf(xd * xd + yd * yd);
-      const float horizon = b.horizon;
-      ep->pf_far = dist > horizon ? 1 : 0;
-      ep->igx = x + (xd * horizon) / (dist + 1e-6f);
-      ep->igy = y + (yd * horizon) / (dist + 1e-6f);
-      ep->pf_scale = 1.0f + (2.0f * horizon) / dist;
-      ep->speed_on = (dist < 2.0f) ? 0 : 1;
-    }
+    episode_goal_fields(ep, x, y, gx, gy, b.horizon);
     ep->cur = cur_buf ^ 1;
     ep->step = ep->step + 1;
     ep->steps_run = row + 1;
@@ -387,6 +420,52 @@ __global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b,
   campaign_refill(b, q, e, b.ep + e, true, (int)threadIdx.x, 64, &got);
 }
 
+// The way into the episode record for a plant that lives on the device (mppi_batch_step_device):
+// episode e takes this step iff it is set (is_set[e], the host's flag mirrored in device memory) and
+// io.mask lets it; its record then takes the state of io.states[e] (11 floats in mppi_state order,
+// the heading as given) and the critics' scalar parts of that state, and `reached` is cleared (no
+// goal test has seen the new state).  On a reset the workgroup zeroes both halves of the nominal
+// double buffer and the lane restarts the step index, the buffer half and, where given, the seed.
+// An episode that does not step keeps its whole record but `active`, which every launch of the
+// step reads.  Grid E, one wave each; e is the workgroup's, so every read is wave-uniform.  No LDS, no
+// waits: the noise and rollout kernels read the record behind the kernel boundary.
+__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
+                                                                const int* __restrict__ is_set) {
+  const int e = blockIdx.x;
+  BatchEpisode* ep = b.ep + e;
+  const bool on = is_set[e] != 0 && (!io.mask || io.mask[e] != 0);
+  const bool reset = on && io.reset && io.reset[e] != 0;
+  if (threadIdx.x == 0) {
+    ep->active = on ? 1 : 0;
+    if (on) {
+      const float* s = io.states + (size_t)e * 11;
+      const float x = s[0], y = s[1], gx = s[7], gy = s[8];
+      ep->x0 = x;
+      ep->y0 = y;
+      ep->h0x = s[2];
+      ep->h0y = s[3];
+      ep->h0z = s[4];
+      ep->wl = s[5];
+      ep->wr = s[6];
+      ep->gx = gx;
+      ep->gy = gy;
+      ep->s1 = s[9];
+      ep->s2 = s[10];
+      episode_goal_fields(ep, x, y, gx, gy, b.horizon);
+      ep->reached = 0;
+      if (reset) {
+        ep->cur = 0;
+        ep->step = 0;
+        if (io.seeds) ep->seed = io.seeds[e];
+      }
+    }
+  }
+  if (reset) {
+    float* u = b.unom + (size_t)e * 4 * b.H;
+    for (int j = (int)threadIdx.x; j < 4 * b.H; j += 64) u[j] = 0.0f;
+  }
+}
+
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
   // about four wave-units (two noise_waves iterations) per wave
   const int units = b.blocks * ((b.H + 1) >> 1) * 4;
@@ -406,6 +485,17 @@ hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t
 
 hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st) {
   hipLaunchKernelGGL(mppi_batch_finish_kernel<>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_ingest_kernel, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchIo>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, io);
   return hipGetLastError();
 }
 

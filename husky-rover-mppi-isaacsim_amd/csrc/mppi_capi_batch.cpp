@@ -36,6 +36,11 @@ struct mppi_batch {
   Event ev[2];
   double last_ms = 0;
   bool failed = false;  // a HIP error of the batch: further runs are refused
+  // mppi_batch_step_device: is_set in device memory (the ingest kernel's `active` rule), and whether
+  // steps were enqueued that no synchronous call has waited for yet (a HIP error of theirs surfaces
+  // in that call, which then refuses the batch as a failed run does)
+  DeviceBuf<int> d_set;
+  bool unwaited = false;
   // per-episode parameter variants (mppi_batch_set_variants / _set_episode_variant)
   std::vector<mppi_batch_variant> variants;  // the table as last set
   std::vector<int> ep_var;                   // [E] each episode's row, -1: none
@@ -298,6 +303,46 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   return MPPI_OK;
 }
 
+// One step of the set episodes from states in device memory: ingest, noise, a rollout per projection
+// in use, the finish's step form.  Enqueues and returns: no wait, no copy, no read of pinned memory.
+// Everything the host decides comes from its own bookkeeping (is_set, ep_var, variants, book).
+int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in) {
+  mppi_ctx* c = b->c;
+  const Plan pl = make_plan(c);
+  bool any_set = false, any_var = false, use_proj[4] = {false, false, false, false};
+  for (int e = 0; e < b->E; ++e) {
+    if (!b->is_set[e]) continue;
+    any_set = true;
+    const int vi = b->ep_var[e];
+    any_var = any_var || vi >= 0;
+    use_proj[vi >= 0 ? b->variants[vi].proj : proj] = true;
+  }
+  if (!any_set) return MPPI_OK;  // no episode takes the step
+  RolloutArgs a;
+  FinishArgs f;
+  step_args(c, pl, a, f);
+  // (the step form of the finish reads no policy field: no advance, no goal test)
+  BatchArgs z = batch_args(b, proj, mppi_loop_policy{0.0f, 1.0f, 0.0f, 0});
+  z.var = any_var ? b->d_var : nullptr;
+  z.log = b->log;
+  z.log_cap = b->log_cap;
+  z.scene = b->book.need_table() ? b->d_tab.get() : nullptr;
+  BatchIo io;
+  io.states = io_in.states;
+  io.mask = io_in.mask;
+  io.reset = io_in.reset;
+  io.seeds = io_in.seeds;
+  io.cmd = io_in.cmd;
+  io.plan = io_in.plan;
+  b->unwaited = true;
+  HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
+  HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+  for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
+    if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
+  HIP_TRY(launch_batch_finish_step(f, z, io, pl.fin_lds_bytes, c->stream));
+  return MPPI_OK;
+}
+
 // ---- the task queue ----
 
 // An entry point that writes an episode's record or its row of the device's tables, while the
@@ -318,6 +363,7 @@ int campaign_restore(mppi_batch* b) {
   HIP_TRY(hipMemcpyAsync(b->d_ep_var, b->ep_var.data(), E * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(b->d_tab->rec, recs.data(), E * sizeof(BatchScene), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->ep, 0, E * sizeof(BatchEpisode), c->stream));
+  HIP_TRY(hipMemsetAsync(b->d_set, 0, E * sizeof(int), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // recs is pageable and dies here
   b->host.assign(E, BatchEpisode{});
   b->is_set.assign(E, 0);
@@ -557,7 +603,8 @@ int mppi_batch_create(mppi_ctx* c, int32_t episodes, mppi_batch** out) {
   for (size_t e = 0; e < E; ++e) recs[e] = b->book.record((int)e);
   const size_t tab_bytes = offsetof(BatchSceneTable, rec) + E * sizeof(BatchScene);
   if (b->ep.alloc(E * sizeof(BatchEpisode)) || b->d_var.alloc(kBatchMaxVariants * sizeof(BatchVariant)) ||
-      b->d_ep_var.alloc(E * sizeof(int)) || b->d_tab.alloc(tab_bytes) ||
+      b->d_ep_var.alloc(E * sizeof(int)) || b->d_tab.alloc(tab_bytes) || b->d_set.alloc(E * sizeof(int)) ||
+      hipMemset(b->d_set, 0, E * sizeof(int)) != hipSuccess ||
       hipMemset(b->d_tab, 0, tab_bytes) != hipSuccess ||
       hipMemcpy(b->d_tab->rec, recs.data(), E * sizeof(BatchScene), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(b->d_var, 0, kBatchMaxVariants * sizeof(BatchVariant)) != hipSuccess ||
@@ -618,6 +665,7 @@ int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, ui
   b->book.mark_set(e);
   HIP_TRY(hipMemcpyAsync(b->ep + e, &b->host[e], sizeof(BatchEpisode), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->unom + (size_t)e * 4 * b->H, 0, (size_t)4 * b->H * sizeof(float), c->stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(b->d_set + e), 1, 1, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return MPPI_OK;
 }
@@ -641,9 +689,53 @@ int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop
   return rc;
 }
 
+int mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!io) return fail(MPPI_EINVAL, "batch_step_device: null io");
+  if (!io->states) return fail(MPPI_EINVAL, "batch_step_device: null states");
+  if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;  // (a host wait only while a resident server is running)
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (int rc = campaign_busy(b, "batch_step_device")) return rc;
+  if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
+  if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
+  if (int rc_g = scene_geometry(b)) return rc_g;
+  const Plan pl = make_plan(c);
+  if (!pl.roles || pl.blocks != b->blocks)
+    return fail(MPPI_ESTATE, "batch: the context does not run the role-split rollout plan (MPPI_ROLES=0)");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = batch_step_device(b, proj, *io);
+  if (rc == MPPI_EHIP) b->failed = true;
+  return rc;
+}
+
+// The two readers below wait for the stream: a HIP error of steps that mppi_batch_step_device
+// enqueued surfaces in them, and refuses the batch as a failed run does.
+static int after_wait(mppi_batch* b, int rc) {
+  if (rc == MPPI_EHIP && b->unwaited) b->failed = true;
+  if (rc == MPPI_OK) b->unwaited = false;
+  return rc;
+}
+static int get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total, int32_t* steps_last_run,
+                       int32_t* reached, float* u1, float* u2);
+static int get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows);
+
 int mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total,
                            int32_t* steps_last_run, int32_t* reached, float* u1, float* u2) {
   if (int rc = batch_episode(b, e)) return rc;
+  return after_wait(b, get_episode(b, e, state, steps_total, steps_last_run, reached, u1, u2));
+}
+
+int mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "log range out of bounds");
+  if (count > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  return after_wait(b, get_log(b, e, first, count, rows));
+}
+
+static int get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t* steps_total, int32_t* steps_last_run,
+                       int32_t* reached, float* u1, float* u2) {
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
@@ -674,10 +766,7 @@ int mppi_batch_get_episode(mppi_batch* b, int32_t e, mppi_state* state, int64_t*
   return MPPI_OK;
 }
 
-int mppi_batch_get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows) {
-  if (int rc = batch_episode(b, e)) return rc;
-  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "log range out of bounds");
-  if (count > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+static int get_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows) {
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));

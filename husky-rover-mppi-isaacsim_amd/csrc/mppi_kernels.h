@@ -311,6 +311,25 @@ struct BatchCampaign {
 hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st);
 hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
                                         hipStream_t st);
+// ---- the device-resident step of a batch (mppi_batch_step_device) ----
+// One step of every set episode for a plant that is not the controller's own model: the ingest
+// kernel writes the caller's states into the episode records, the noise and rollout kernels run as
+// in any step, and the finish kernel's step form hands the command and the plan out instead of
+// advancing.  mppi_batch_io (include/mppi.h) field for field: device pointers, the finish form's
+// own third kernel argument (BatchArgs does not grow).
+struct BatchIo {
+  const float* states;    // [E][11] mppi_state field order
+  const int* mask;        // [E] or null
+  const int* reset;       // [E] or null
+  const uint64_t* seeds;  // [E] or null
+  float* cmd;             // [E][2] or null
+  float* plan;            // [E][4H + 12] or null
+};
+static_assert(sizeof(BatchIo) == 48, "BatchIo layout");
+// is_set: [E] the host's "mppi_batch_set_episode was called" flags in device memory
+hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st);
+hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
+                                    hipStream_t st);
 
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);

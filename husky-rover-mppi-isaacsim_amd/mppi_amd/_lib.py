@@ -88,6 +88,11 @@ class MppiBatchTask(C.Structure):
                 ("costmap_slot", C.c_int32), ("num_trajectories", C.c_int64), ("max_steps", C.c_int32)]
 
 
+class MppiBatchIo(C.Structure):
+    """mppi_batch_io: the device pointers of one mppi_batch_step_device call (any but states may be NULL)."""
+    _fields_ = [(n, C.c_void_p) for n in ("states", "mask", "reset", "seeds", "cmd", "plan")]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
 
 
@@ -158,6 +163,7 @@ _PROTOS = {
     "mppi_batch_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MppiLoopPolicy)]),
     "mppi_batch_get_episode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiState), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, _FP]),
+    "mppi_batch_step_device": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchIo)]),
     "mppi_batch_get_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "mppi_batch_get_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_batch_variant_default": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiLoopPolicy),
@@ -218,6 +224,51 @@ def load_library(path: str = LIB_PATH):
 
 def _fp(a):
     return a.ctypes.data_as(_FP)
+
+
+_DTYPE_NAMES = {"f4": "float32", "i4": "int32", "u8": "uint64", "i8": "int64"}
+
+
+def device_array(a, what, codes=("f4",)):
+    """(device pointer, shape, keepalive, device index or None) of a GPU-resident array, taken zero
+    copy; None for anything that is not one (a host array).
+
+    Accepted: an object exposing ``__cuda_array_interface__`` (a Warp array), a CUDA
+    ``torch.Tensor``, or a ``__dlpack__`` producer on the GPU (viewed as a tensor, no copy).  The
+    element type must be one of `codes` (array-interface codes: "f4", "i4", "u8", "i8") and the array
+    C-contiguous: ValueError otherwise, naming `what` (a silent copy would stop following the
+    caller's buffer).  The device index is known for tensors only.
+    """
+    want = " or ".join(_DTYPE_NAMES[c] for c in codes)
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape = tuple(int(n) for n in cai["shape"])
+        ts = cai.get("typestr")
+        if not isinstance(ts, str) or ts.lstrip("<=|") not in codes:
+            raise ValueError(f"{what} must be {want}, got typestr {ts!r}")
+        item = int(ts.lstrip("<=|")[1:])
+        strides = cai.get("strides")
+        if strides is not None and tuple(strides) != tuple(
+                item * int(np.prod(shape[i + 1:])) for i in range(len(shape))):
+            raise ValueError(f"{what} must be C-contiguous, got strides {strides}")
+        return int(cai["data"][0]), shape, a, None
+    try:
+        import torch
+    except ImportError:
+        return None
+    if not isinstance(a, torch.Tensor) and hasattr(a, "__dlpack__"):
+        dev = a.__dlpack_device__()[0] if hasattr(a, "__dlpack_device__") else None
+        if dev in (2, 10):  # kDLCUDA, kDLROCM: a device producer, viewed as a tensor (no copy)
+            a = torch.from_dlpack(a)
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        ok = [getattr(torch, _DTYPE_NAMES[c]) for c in codes if hasattr(torch, _DTYPE_NAMES[c])]
+        if a.dtype not in ok:
+            raise ValueError(f"{what} must be {want}, got {a.dtype}")
+        if not a.is_contiguous():
+            raise ValueError(f"{what} must be contiguous (pass a contiguous buffer: a copy would not "
+                             "follow the caller's updates)")
+        return a.data_ptr(), tuple(int(n) for n in a.shape), a, a.device.index
+    return None
 
 
 def _obstacles(obstacles):
@@ -808,6 +859,59 @@ class Batch:
         """Advance every active episode by up to n_steps steps (policy: MppiLoopPolicy, default run()'s)."""
         pol = policy if policy is not None else make_policy()
         _check(self.lib, self.lib.mppi_batch_run(self.h, PROJ[proj], int(n_steps), C.byref(pol)), "mppi_batch_run")
+
+    def _io_array(self, a, name, codes, shape):
+        """The device pointer of one array of step_device, checked: a device array (device_array's
+        rules) of the given element type and shape on the engine's device."""
+        dev = device_array(a, name, codes)
+        if dev is None:
+            raise TypeError(f"{name} must be a device array (a CUDA torch.Tensor, or an object exposing "
+                            f"__cuda_array_interface__ or __dlpack__ on the GPU), got {type(a).__name__}")
+        ptr, shp, _, index = dev
+        if shp != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {shp}")
+        if index is not None and index != self.engine.device:
+            raise ValueError(f"{name} is on device {index}, the engine's is {self.engine.device}")
+        return ptr
+
+    def step_device(self, states, mask=None, reset=None, seeds=None, cmd=None, plan=None, proj="3d"):
+        """mppi_batch_step_device: one step of every set episode from states held on the device, for a
+        plant that is not the controller's own model.  Enqueues on the engine's stream and returns;
+        it never synchronises, so the arrays are read and written in stream order and must stay
+        alive until the step has run.
+
+        states: float32 [E, 11] in mppi_state field order (mppi_amd.batch.pack_states), the heading
+        used as given; mask, reset: int32 [E] or None (episode e steps iff mask[e] != 0; reset[e] != 0
+        restarts it first: zero nominal sequence, step index 0); seeds: uint64 or int64 [E] or None,
+        the new Philox key where reset[e] != 0; cmd: float32 [E, 2] (v, w); plan: float32
+        [E, 4H + 12] (u1_opt, u2_opt, lin_vel, ang_vel [H] each, then row 0 of traj_sim, heading_sim,
+        left_wheel_sim, right_wheel_sim).  Every array is a device array taken zero copy (a CUDA
+        torch.Tensor, __cuda_array_interface__, a DLPack producer), contiguous, on the engine's
+        device.  cmd / plan not given are allocated as torch tensors (uninitialised: the rows of an
+        episode that does not step are not written).  Returns (cmd, plan).
+        """
+        E, H = self.E, self.H
+        io = MppiBatchIo()
+        io.states = self._io_array(states, "states", ("f4",), (E, 11))
+        if mask is not None:
+            io.mask = self._io_array(mask, "mask", ("i4",), (E,))
+        if reset is not None:
+            io.reset = self._io_array(reset, "reset", ("i4",), (E,))
+        if seeds is not None:
+            io.seeds = self._io_array(seeds, "seeds", ("u8", "i8"), (E,))
+        if proj not in PROJ:
+            raise ValueError(f"proj must be one of {sorted(map(str, PROJ))}, got {proj!r}")
+        if cmd is None or plan is None:
+            import torch
+            device = torch.device("cuda", self.engine.device)
+            if cmd is None:
+                cmd = torch.empty((E, 2), dtype=torch.float32, device=device)
+            if plan is None:
+                plan = torch.empty((E, 4 * H + 12), dtype=torch.float32, device=device)
+        io.cmd = self._io_array(cmd, "cmd", ("f4",), (E, 2))
+        io.plan = self._io_array(plan, "plan", ("f4",), (E, 4 * H + 12))
+        _check(self.lib, self.lib.mppi_batch_step_device(self.h, PROJ[proj], C.byref(io)), "mppi_batch_step_device")
+        return cmd, plan
 
     def episode(self, e):
         """dict(state (MppiState), steps_total, steps_last_run, reached, u1, u2 (the next nominal sequence))."""

@@ -224,6 +224,29 @@ def state_dict(x, y, heading=(1.0, 0.0, 0.0), left_wheel_speed=0.0, right_wheel_
                 goal_x=F32(goal_x), goal_y=F32(goal_y), std_dev_u1=F32(std_dev_u1), std_dev_u2=F32(std_dev_u2))
 
 
+STATE_WIDTH = 11    # floats of mppi_state: the row of Batch.step_device's `states`
+
+
+def pack_states(states):
+    """State dicts -> float32 [E, 11], the rows Batch.step_device reads: x, y, heading[3],
+    left_wheel_speed, right_wheel_speed, goal_x, goal_y, std_dev_u1, std_dev_u2 (mppi_state's field
+    order; the heading as given).  Upload it once, then keep the rows current on the device."""
+    out = np.zeros((len(states), STATE_WIDTH), dtype=F32)
+    for e, s in enumerate(states):
+        h = np.asarray(s["heading"], dtype=F32).reshape(3)
+        out[e] = (s["x"], s["y"], h[0], h[1], h[2], s["left_wheel_speed"], s["right_wheel_speed"],
+                  s["goal_x"], s["goal_y"], s["std_dev_u1"], s["std_dev_u2"])
+    return out
+
+
+def unpack_states(rows):
+    """The inverse of pack_states: float32 [E, 11] -> list of state dicts."""
+    rows = np.asarray(rows, dtype=F32)
+    if rows.ndim != 2 or rows.shape[1] != STATE_WIDTH:
+        raise ValueError(f"states must have shape (E, {STATE_WIDTH}), got {rows.shape}")
+    return [state_dict(r[0], r[1], r[2:5], r[5], r[6], r[7], r[8], r[9], r[10]) for r in rows]
+
+
 def to_mppi_state(state):
     """The ctypes MppiState of a state dict (the heading as given, no renormalisation)."""
     from . import _lib

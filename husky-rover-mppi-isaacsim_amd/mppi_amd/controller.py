@@ -18,7 +18,7 @@ import numpy as np
 import yaml
 
 from . import _lib, scene
-from .batch import campaign_tasks, episode_scenes
+from .batch import campaign_tasks, episode_scenes, to_mppi_state
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CONFIG = os.path.join(_HERE, "config.yaml")
@@ -488,6 +488,57 @@ class MPPI_Controller:
             self.loop += 1
         print("Number of loops:", self.loop)
 
+    def _open_batch(self, E, states, seeds, variants, episode_variant, dems, costmaps, episode_dem, episode_costmap,
+                    episode_trajectories):
+        """The set-up run_batch and batch_stepper share: the per-episode arguments checked, then a
+        _lib.Batch of E episodes with its variant table and scene slots filled and every episode set
+        (states(): one MppiState per episode, asked for once the engine is up).  The caller closes it."""
+        seeds = [self.seed + e for e in range(E)] if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != E:
+            raise ValueError(f"{E} episodes but {len(seeds)} seeds")
+        ev = [-1] * E if episode_variant is None else [-1 if v is None else int(v) for v in episode_variant]
+        if len(ev) != E:
+            raise ValueError(f"{E} episodes but {len(ev)} variant indices")
+        if any(v >= 0 for v in ev) and not variants:
+            raise ValueError("episode_variant names rows of `variants`, which is empty")
+        ed, ec, ek = episode_scenes(E, self.number_of_trajectories, dems, costmaps, episode_dem, episode_costmap,
+                                    episode_trajectories)
+        if self.engine is None:
+            self.warp_setup()
+        states = states()
+        batch = _lib.Batch(self.engine, E)
+        try:
+            if variants:
+                batch.set_variants(variants)
+            for slot, Z in enumerate(dems or []):
+                Z = np.asarray(Z, np.float32)
+                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
+            for slot, cm in enumerate(costmaps or []):
+                self._fill_costmap_slot(batch, slot, cm)
+            for e in range(E):
+                batch.set_episode(e, states[e], seeds[e], ev[e], ed[e], ec[e], ek[e])
+        except Exception:
+            batch.close()
+            raise
+        return batch
+
+    def batch_stepper(self, episodes, seeds=None, variants=None, episode_variant=None, dems=None, costmaps=None,
+                      episode_dem=None, episode_costmap=None, episode_trajectories=None):
+        """E controllers for E rovers of an external, vectorised simulator (mppi_batch_step_device,
+        DESIGN.md §3.7): the Isaac loop (visual_terrain_stack_full_terrain.py:466-515) with the poses
+        kept in device tensors.  episodes: the E initial states (state dicts of mppi_amd.batch, or
+        MppiState); every step replaces them with the states it is given.  seeds, variants,
+        episode_variant, dems, costmaps, episode_dem, episode_costmap, episode_trajectories: as
+        run_batch.
+
+        Returns a BatchStepper: .step(states, mask=None, reset=None, seeds=None, proj="3d") ->
+        (cmd [E, 2], plan [E, 4H + 12]) device tensors (Batch.step_device; the same two tensors at
+        every step, so read them in stream order), .batch (the _lib.Batch) and .close().
+        """
+        states = [s if isinstance(s, _lib.MppiState) else to_mppi_state(s) for s in episodes]
+        return BatchStepper(self._open_batch(len(states), lambda: states, seeds, variants, episode_variant, dems, costmaps, episode_dem,
+                                             episode_costmap, episode_trajectories))
+
     def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None,
                   variants=None, episode_variant=None, score=None, dems=None, costmaps=None, episode_dem=None,
                   episode_costmap=None, episode_trajectories=None):
@@ -525,32 +576,12 @@ class MPPI_Controller:
         E = starts.shape[0]
         headings = np.asarray(headings, np.float64).reshape(E, 3)
         goals = np.asarray(goals, np.float64).reshape(E, 2)
-        seeds = [self.seed + e for e in range(E)] if seeds is None else [int(s) for s in seeds]
-        if len(seeds) != E:
-            raise ValueError(f"{E} episodes but {len(seeds)} seeds")
-        ev = [-1] * E if episode_variant is None else [-1 if v is None else int(v) for v in episode_variant]
-        if len(ev) != E:
-            raise ValueError(f"{E} episodes but {len(ev)} variant indices")
-        if any(v >= 0 for v in ev) and not variants:
-            raise ValueError("episode_variant names rows of `variants`, which is empty")
-        ed, ec, ek = episode_scenes(E, self.number_of_trajectories, dems, costmaps, episode_dem, episode_costmap,
-                                    episode_trajectories)
-        if self.engine is None:
-            self.warp_setup()
         pol = _lib.make_policy(**(policy or {}))
-        batch = _lib.Batch(self.engine, E)
+        batch = self._open_batch(
+            E, lambda: [_lib.make_state(starts[e, 0], starts[e, 1], headings[e], 0.0, 0.0, goals[e, 0], goals[e, 1],
+                                        self.std_dev_u1, self.std_dev_u2) for e in range(E)],
+            seeds, variants, episode_variant, dems, costmaps, episode_dem, episode_costmap, episode_trajectories)
         try:
-            if variants:
-                batch.set_variants(variants)
-            for slot, Z in enumerate(dems or []):
-                Z = np.asarray(Z, np.float32)
-                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
-            for slot, cm in enumerate(costmaps or []):
-                self._fill_costmap_slot(batch, slot, cm)
-            for e in range(E):
-                batch.set_episode(e, _lib.make_state(starts[e, 0], starts[e, 1], headings[e], 0.0, 0.0,
-                                                     goals[e, 0], goals[e, 1], self.std_dev_u1, self.std_dev_u2),
-                                  seeds[e], ev[e], ed[e], ec[e], ek[e])
             batch.run(self.max_loops if max_loops is None else int(max_loops), proj, pol)
             out = []
             for e in range(E):
@@ -626,6 +657,30 @@ class MPPI_Controller:
             batch.close()
 
 
+class BatchStepper:
+    """What MPPI_Controller.batch_stepper returns: a filled _lib.Batch stepped from device tensors.
+    cmd and plan are allocated once, at the first step, and reused."""
+
+    def __init__(self, batch):
+        self.batch = batch
+        self.cmd = None
+        self.plan = None
+
+    def step(self, states, mask=None, reset=None, seeds=None, proj="3d"):
+        """Batch.step_device with the stepper's own cmd / plan tensors; never synchronises."""
+        self.cmd, self.plan = self.batch.step_device(states, mask, reset, seeds, self.cmd, self.plan, proj)
+        return self.cmd, self.plan
+
+    def close(self):
+        self.batch.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _is_costmap_array(cm, shape):
     """A costmap given as an array (2-D of `shape`, or flat) rather than as a rock list."""
     if isinstance(cm, dict):
@@ -649,31 +704,9 @@ def _grid_shape(shape):
 def _device_dem(Z):
     """(device pointer, rows, cols, keepalive) for a GPU-resident float32 C-contiguous DEM, None for a
     host array; raises for a device array that would need a copy."""
-    cai = getattr(Z, "__cuda_array_interface__", None)
-    if cai is not None:
-        shape = tuple(cai["shape"])
-        if cai.get("typestr") not in ("<f4", "=f4", "f4"):
-            raise ValueError(f"device DEM must be float32, got typestr {cai.get('typestr')!r}")
-        strides = cai.get("strides")
-        if strides is not None and tuple(strides) != tuple(
-                4 * int(np.prod(shape[i + 1:])) for i in range(len(shape))):
-            raise ValueError(f"device DEM must be C-contiguous, got strides {strides}")
-        rows, cols = _grid_shape(shape)
-        return int(cai["data"][0]), rows, cols, Z
-    try:
-        import torch
-    except ImportError:
-        torch = None
-    if torch is not None and not isinstance(Z, torch.Tensor) and hasattr(Z, "__dlpack__"):
-        dev = Z.__dlpack_device__()[0] if hasattr(Z, "__dlpack_device__") else None
-        if dev in (2, 10):  # kDLCUDA, kDLROCM: a device producer, viewed as a tensor (no copy)
-            Z = torch.from_dlpack(Z)
-    if torch is not None and isinstance(Z, torch.Tensor) and Z.is_cuda:
-        if Z.dtype != torch.float32:
-            raise ValueError(f"device DEM must be float32, got {Z.dtype}")
-        if not Z.is_contiguous():
-            raise ValueError("device DEM must be contiguous (bind a contiguous buffer: a copy would not "
-                             "follow the caller's updates)")
-        rows, cols = _grid_shape(tuple(Z.shape))
-        return Z.data_ptr(), rows, cols, Z
-    return None
+    dev = _lib.device_array(Z, "device DEM")   # (the rules Batch.step_device applies to its arrays)
+    if dev is None:
+        return None
+    ptr, shape, keep, _ = dev
+    rows, cols = _grid_shape(shape)
+    return ptr, rows, cols, keep

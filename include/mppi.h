@@ -489,6 +489,50 @@ int  mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t co
 int  mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
                             mppi_path_scores* out, int32_t* rows);
 
+/* ---- a batch's device-resident step: the plant is the caller's ----
+ * mppi_batch_run feeds row 0 of the optimal rollout back as the next state: the plant is the
+ * controller's own model.  The Isaac loop (visual_terrain_stack_full_terrain.py:466-515) hands
+ * optimal_lin_vel_wp[0] / optimal_ang_vel_wp[0] to a simulator, reads the pose, heading and angular
+ * velocity back from it and computes the sigmas from the measured angular velocity.  A vectorised
+ * simulator of E rovers holds those in device memory; this call takes the states from there and
+ * leaves the commands there, one step of every episode per call, with no host copy in between.
+ * Asynchronous on the context's stream (the caller's after mppi_set_stream): the call enqueues the
+ * launches (ingest, normals, one rollout per projection in use, finish) and returns, without a
+ * stream wait, a host copy or a read of pinned memory.  It stops the context's resident server
+ * first, as every batch call does: a host wait only while a server is running.  The arrays are read
+ * and written in stream order; the caller keeps them alive until the step has run.  A HIP error of
+ * an enqueued step surfaces at the next synchronous call of the batch (mppi_batch_get_episode,
+ * _get_log, _run), which then refuses the batch as a failed run does (MPPI_ESTATE from then on).
+ * Contract: for every set episode e that takes the step, cmd[e] and plan[e] are bitwise lin_vel[0],
+ * ang_vel[0] and the listed outputs of mppi_step(ctx', proj_e, s_e), ctx' a context with the batch
+ * context's params overridden by e's variant, num_trajectories = K_e, e's seed, DEM and costmap,
+ * after mppi_set_state(states[e]) and with the nominal sequence e's previous step left (zero after
+ * mppi_batch_set_episode or a reset); s_e = the steps e has taken since mppi_batch_set_episode or
+ * its last reset.  Afterwards the new nominal sequence is the one the next step reads, s_e and
+ * steps_total have grown by one, and e's record holds states[e] (what mppi_batch_get_episode
+ * reports; `reached` reads 0: no goal test has seen that state).  No advance rule, no goal test, no
+ * log row: steps_last_run and the log stay as the last mppi_batch_run left them.
+ * An episode that is masked out or was never set does not step: its state, nominal sequence and
+ * step index stay as they are and its rows of cmd and plan are not written.
+ * proj applies to the episodes without a variant.  MPPI_EINVAL for a null io or null states;
+ * MPPI_ESTATE without a DEM and costmap, while a campaign is unfinished, when a held slot's geometry
+ * is no longer the context's, after a HIP error of the batch, and when the context does not run the
+ * role-split plan.  May be mixed with mppi_batch_run, which continues from the record the last
+ * device step left. */
+typedef struct mppi_batch_io {   /* device pointers, on the batch context's device */
+  const float*    states; /* [E][11] rows in mppi_state field order: x, y, heading[3],
+                             left_wheel_speed, right_wheel_speed, goal_x, goal_y,
+                             std_dev_u1, std_dev_u2; heading used as given (as mppi_set_state) */
+  const int32_t*  mask;   /* [E] or NULL: episode e takes this step iff mask[e] != 0 (NULL: all set episodes) */
+  const int32_t*  reset;  /* [E] or NULL: reset[e] != 0 restarts e before the step: zero nominal
+                             sequence, step index 0, and seeds[e] as its Philox key if seeds != NULL */
+  const uint64_t* seeds;  /* [E] or NULL; read only where reset[e] != 0 */
+  float*          cmd;    /* [E][2] or NULL: v, w = element 0 of the filtered optimal velocities */
+  float*          plan;   /* [E][4H+12] or NULL: u1_opt, u2_opt, lin_vel, ang_vel [H] each, then row 0 of
+                             traj_sim, heading_sim, left_wheel_sim, right_wheel_sim */
+} mppi_batch_io;
+int  mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io);
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

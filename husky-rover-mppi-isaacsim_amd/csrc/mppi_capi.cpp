@@ -1209,6 +1209,17 @@ static int build_normal_table(mppi_ctx* c) {
 int mppi_set_dem(mppi_ctx* c, const float* z, int32_t rows, int32_t cols, float x_min, float y_min,
                  float resolution) {
   if (!c || !z) return fail(MPPI_EINVAL, "null argument");
+  return install_dem(c, rows, cols, x_min, y_min, resolution, [&](float* dst) {
+    HIP_TRY(hipMemcpyAsync(dst, z, (size_t)rows * cols * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return (int)MPPI_OK;
+  });
+}
+
+// mppi_set_dem from the quiesce on.  `fill(dst)` enqueues the heights into the context's own DEM
+// buffer on the context stream (mppi_set_dem: the copy from the host; mppi_build_dem: the product
+// kernel); the stream is waited for before the geometry changes.
+extern "C++" int mppi::capi::install_dem(mppi_ctx* c, int32_t rows, int32_t cols, float x_min, float y_min,
+                                         float resolution, const std::function<int(float*)>& fill) {
   if (int rc_q = quiesce(c)) return rc_q;
   int rc = check_grid(rows, cols, resolution);
   if (rc) return rc;
@@ -1220,7 +1231,8 @@ int mppi_set_dem(mppi_ctx* c, const float* z, int32_t rows, int32_t cols, float 
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(c->dem.Z.alloc(bytes));
   }
-  HIP_TRY(hipMemcpyAsync(c->dem.Z, z, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = fill(c->dem.Z);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->dem.rows = rows;
   c->dem.cols = cols;

@@ -859,11 +859,31 @@ int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
 int mppi_batch_set_dem(mppi_batch* b, int32_t slot, const float* z_host) {
   if (int rc = slot_index(b, kSceneDem, slot)) return rc;
   mppi_ctx* c = b->c;
+  if (!z_host) {
+    if (int rc_q = quiesce(c)) return rc_q;
+    HIP_TRY(hipSetDevice(c->device));
+    return slot_free(b, kSceneDem, slot);
+  }
+  return batch_fill_dem(b, slot, "batch_set_dem", [&](float* dst) {
+    HIP_TRY(hipMemcpyAsync(dst, z_host, (size_t)c->dem.rows * c->dem.cols * sizeof(float), hipMemcpyHostToDevice,
+                           c->stream));
+    return (int)MPPI_OK;
+  });
+}
+
+// What mppi_capi_dem.cpp needs of a batch, whose layout stays in this file.
+extern "C++" mppi_ctx* mppi::capi::batch_context(mppi_batch* b) { return b->c; }
+extern "C++" int mppi::capi::batch_dem_slot(const mppi_batch* b, int32_t slot) { return slot_index(b, kSceneDem, slot); }
+
+// mppi_batch_set_dem for heights that `fill(dst)` enqueues on the context stream into the slot's
+// buffer (the copy from the host, or mppi_batch_build_dem's product kernel); slot is in range.
+extern "C++" int mppi::capi::batch_fill_dem(mppi_batch* b, int32_t slot, const char* who,
+                                            const std::function<int(float*)>& fill) {
+  mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
-  if (!z_host) return slot_free(b, kSceneDem, slot);
   if (!c->dem.Z || c->dem.rows <= 0)
-    return fail(MPPI_ESTATE, "batch_set_dem: no DEM: call mppi_set_dem first (a slot takes the context's geometry)");
+    return fail(MPPI_ESTATE, std::string(who) + ": no DEM: call mppi_set_dem first (a slot takes the context's geometry)");
   const int rows = c->dem.rows, cols = c->dem.cols;
   const size_t zb = (size_t)rows * cols * sizeof(float);
   const size_t nb = ((size_t)rows + 1) * ((size_t)cols + 1) * sizeof(float4);
@@ -872,6 +892,8 @@ int mppi_batch_set_dem(mppi_batch* b, int32_t slot, const float* z_host) {
   DeviceBuf<float4> nt;
   if (int rc = slot_alloc(d.Z, nz, zb, "DEM", slot)) return rc;
   if (int rc = slot_alloc(d.ntab, nt, nb, "DEM", slot)) return rc;
+  // (filled before a new buffer replaces the slot's: a fill that fails leaves a live slot's buffers in place)
+  if (int rc = fill(nz ? nz.get() : d.Z.get())) return rc;
   if (nz) d.Z = std::move(nz);
   if (nt) d.ntab = std::move(nt);
   d.rows = rows;
@@ -882,7 +904,6 @@ int mppi_batch_set_dem(mppi_batch* b, int32_t slot, const float* z_host) {
   d.rinv_res = c->dem.rinv_res;
   const float* zp = d.Z;
   const float4* np = d.ntab;
-  HIP_TRY(hipMemcpyAsync(d.Z, z_host, zb, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(launch_normal_table(d.Z, rows, cols, d.res, d.ntab, c->stream));
   HIP_TRY(hipMemcpyAsync(b->d_tab->dem_z + slot, &zp, sizeof(zp), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(b->d_tab->dem_ntab + slot, &np, sizeof(np), hipMemcpyHostToDevice, c->stream));

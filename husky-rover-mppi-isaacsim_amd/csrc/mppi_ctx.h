@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -311,6 +312,16 @@ int enqueue_rollout(mppi_ctx* c, int proj, uint64_t step, int mode, const Plan& 
 int enqueue_finish(mppi_ctx* c, const Plan& pl, const mppi_state& st, const double* recs, int n, int mode,
                    double* record_out, bool timed);
 int copy_outputs(mppi_ctx* c, mppi_outputs* out);
+int install_dem(mppi_ctx* c, int32_t rows, int32_t cols, float x_min, float y_min, float resolution,
+                const std::function<int(float*)>& fill);
+// mppi_capi_batch.cpp
+mppi_ctx* batch_context(mppi_batch* b);
+int batch_dem_slot(const mppi_batch* b, int32_t slot);  // MPPI_EINVAL, naming the slot, outside the table
+int batch_fill_dem(mppi_batch* b, int32_t slot, const char* who, const std::function<int(float*)>& fill);
+// mppi_capi_dem.cpp: n craters into `dst` (device, grid x grid floats) on `st`, copied to out_host when
+// given; ends synchronised.  The factor tables live for the call only (2 x 2n x grid doubles).
+int build_dem_into(hipStream_t st, const double* craters, int32_t n, int32_t grid, double half_width,
+                   const float* base_host, float* dst, float* out_host, int32_t variant);
 // mppi_capi_costmap.cpp
 int build_costmap_into(mppi_ctx* c, const double* obstacles, int32_t n, int32_t size, double half_width,
                        double origin_x, double origin_y, double r_robot, int32_t power, int32_t metric, float* dst,

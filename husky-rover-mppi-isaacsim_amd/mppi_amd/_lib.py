@@ -148,6 +148,15 @@ _PROTOS = {
     "mppi_costmap_builder_build": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_double, C.c_double, C.c_int32, _FP, C.c_void_p, C.c_int32]),
     "mppi_costmap_builder_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mppi_dem_builder_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
+    "mppi_dem_builder_destroy": (None, [C.c_void_p]),
+    "mppi_dem_builder_build": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, _FP, _FP, C.c_void_p,
+                                         C.c_int32]),
+    "mppi_dem_builder_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mppi_dem_builder_product": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _FP,
+                                           C.c_void_p, C.c_int32]),
+    "mppi_build_dem": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, _FP, _FP, C.c_int32]),
+    "mppi_batch_build_dem": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_double, _FP, _FP, C.c_int32]),
     "mppi_group_create": (C.c_int, [C.POINTER(MppiParams), C.c_int32, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_void_p)]),
     "mppi_group_destroy": (None, [C.c_void_p]),
@@ -320,6 +329,88 @@ class CostmapBuilder:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.mppi_costmap_builder_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+DEM_VARIANTS = {"mfma": 0, "valu": 1}   # mppi_dem_variant (include/mppi.h)
+
+
+def _dem_variant(v):
+    if v not in DEM_VARIANTS:
+        raise ValueError(f"DEM variant must be one of {sorted(DEM_VARIANTS)}, got {v!r}")
+    return DEM_VARIANTS[v]
+
+
+def _craters(bumps):
+    """Crater list -> contiguous float64 [n, 4] rows (cx, cy, height, width) (n may be 0).  Accepted: the
+    reference's own shape [((cx, cy), height, width), ...] (MPPI_isaac.py:318) or an (n, 4) array."""
+    from .scene import crater_rows
+    a = crater_rows(bumps)
+    return a, a.ctypes.data_as(_DP)
+
+
+def _dem_base(base, grid_size):
+    if base is None:
+        return None
+    base = np.ascontiguousarray(base, dtype=np.float32)
+    if base.shape != (grid_size, grid_size):
+        raise ValueError(f"base: shape {base.shape}, the DEM's is {(grid_size, grid_size)}")
+    return base
+
+
+class DemBuilder:
+    """Surface.create_surface (MPPI_isaac.py:307-356) on the GPU as a separable float64 sum (DESIGN.md
+    §3.6), no controller context needed.
+
+    build(...) returns the grid_size x grid_size float32 heights as an ndarray; with out_device=<pointer>
+    they are written to caller-owned device memory instead.
+    """
+
+    def __init__(self, device: int = 0):
+        self.lib = load_library()
+        self.device = int(device)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.mppi_dem_builder_create(self.device, C.byref(h)), "mppi_dem_builder_create")
+        self.h = h
+
+    def build(self, bumps, grid_size, half_width, base=None, out_device=None, variant="mfma"):
+        """variant "mfma": the product on the matrix cores; "valu": on the vector ALU (same result up to
+        the order of the sum)."""
+        cr, cptr = _craters(bumps)
+        grid_size = int(grid_size)
+        base = _dem_base(base, grid_size)
+        out = None if out_device is not None else np.empty((grid_size, grid_size), np.float32)
+        _check(self.lib, self.lib.mppi_dem_builder_build(
+            self.h, cptr, cr.shape[0], grid_size, float(half_width), None if base is None else _fp(base),
+            None if out is None else _fp(out), None if out_device is None else C.c_void_p(int(out_device)),
+            _dem_variant(variant)), "mppi_dem_builder_build")
+        return out
+
+    def product(self, r_device, c_device, terms, grid_size, out_device=None, variant="mfma"):
+        """Test hook (mppi_dem_builder_product): the product kernel on caller-supplied device factor
+        tables, both [terms][grid_size] float64, terms a multiple of 4."""
+        grid_size = int(grid_size)
+        out = None if out_device is not None else np.empty((grid_size, grid_size), np.float32)
+        _check(self.lib, self.lib.mppi_dem_builder_product(
+            self.h, C.c_void_p(int(r_device)), C.c_void_p(int(c_device)), int(terms), grid_size,
+            None if out is None else _fp(out), None if out_device is None else C.c_void_p(int(out_device)),
+            _dem_variant(variant)), "mppi_dem_builder_product")
+        return out
+
+    def last_ms(self):
+        ms = C.c_double()
+        _check(self.lib, self.lib.mppi_dem_builder_last_ms(self.h, C.byref(ms)), "mppi_dem_builder_last_ms")
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.mppi_dem_builder_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -504,6 +595,21 @@ class Engine:
                                             None if out is None else _fp(out), _metric(metric)),
                 "mppi_build_costmap")
         self.costmap_shape = (int(size), int(size))
+        return out
+
+    def build_dem(self, bumps, grid_size, half_width, base=None, copy_out=True, variant="mfma"):
+        """Surface.create_surface + set_dem in one device pass (mppi_build_dem): the crater field is
+        built in the engine's own DEM buffer with the geometry set_dem(Z, half_width) gives; returns
+        the heights if copy_out."""
+        cr, cptr = _craters(bumps)
+        grid_size = int(grid_size)
+        base = _dem_base(base, grid_size)
+        out = np.empty((grid_size, grid_size), np.float32) if copy_out else None
+        self._c(self.lib.mppi_build_dem(self.ctx, cptr, cr.shape[0], grid_size, float(half_width),
+                                        None if base is None else _fp(base), None if out is None else _fp(out),
+                                        _dem_variant(variant)), "mppi_build_dem")
+        self.dem_shape = (grid_size, grid_size)
+        self._keep = []
         return out
 
     def rollout_python25d(self, x0, y0, heading, lin_vel, ang_vel, dt, half_width, resolution, bound=20.0):
@@ -798,6 +904,20 @@ class Batch:
         Z = self._slot_array(Z, self.engine.dem_shape, "DEM")
         _check(self.lib, self.lib.mppi_batch_set_dem(self.h, int(slot), None if Z is None else _fp(Z)),
                "mppi_batch_set_dem")
+
+    def build_dem(self, slot, bumps, half_width, base=None, copy_out=False, variant="mfma"):
+        """Engine.build_dem with the grid of the engine's DEM (square, centred, of this half_width), into
+        DEM slot `slot`; returns the heights if copy_out."""
+        cr, cptr = _craters(bumps)
+        shape = self.engine.dem_shape
+        if shape is None:
+            raise RuntimeError("DEM slot: the engine has no DEM yet (a slot takes its geometry)")
+        base = self._slot_array(base, shape, "DEM")
+        out = np.empty(shape, np.float32) if copy_out else None
+        _check(self.lib, self.lib.mppi_batch_build_dem(
+            self.h, int(slot), cptr, cr.shape[0], float(half_width), None if base is None else _fp(base),
+            None if out is None else _fp(out), _dem_variant(variant)), "mppi_batch_build_dem")
+        return out
 
     def set_costmap(self, slot, cm):
         """Costmap slot `slot` holds a copy of cm (the shape of the engine's costmap); None frees the slot."""

@@ -125,9 +125,23 @@ class Surface:
         Z = np.load(filename, allow_pickle=False)
         return X, Y, Z
 
+    # where create_surface computes the crater field: "host" = the reference's numpy loop (default),
+    # "device" = the separable float64 sum on the GPU (csrc/mppi_dem_build.hip; at most one float32
+    # ulp from the host path on about one cell in 10^5)
+    dem_builder = "host"
+
     def create_surface(self, bumps):
         """MPPI_isaac.py:307-356 (crater field)."""
-        Z = scene.crater_dem(self.grid_size, self.half_width, bumps).astype(np.float64)
+        if self.dem_builder == "device":
+            from . import _lib
+            b = getattr(self, "_dem_builder", None)
+            if b is None:
+                b = self._dem_builder = _lib.DemBuilder(self.device)
+            Z = b.build(bumps, self.grid_size, self.half_width).astype(np.float64)
+        elif self.dem_builder == "host":
+            Z = scene.crater_dem(self.grid_size, self.half_width, bumps).astype(np.float64)
+        else:
+            raise ValueError(f"Surface.dem_builder must be 'host' or 'device', got {self.dem_builder!r}")
         x = np.linspace(-self.half_width, self.half_width, self.grid_size)
         X, Y = np.meshgrid(x, x)
         return X, Y, Z
@@ -303,6 +317,9 @@ class MPPI_Controller:
         device DEM call :meth:`dem_updated` (or bind it again).
         """
         hw = self.surface.half_width
+        if isinstance(Z, scene.CraterField):   # built in the engine's own DEM buffer, no upload
+            self.engine.build_dem(Z, self.surface.grid_size, hw, base=Z.base, copy_out=False)
+            return
         dev = _device_dem(Z)
         if dev is not None:
             ptr, rows, cols, keep = dev
@@ -328,6 +345,15 @@ class MPPI_Controller:
             n = int(round(np.sqrt(cm.size)))
             cm = cm.reshape(n, n)
         self.engine.set_costmap(cm, self.surface.half_width, self.surface.costmap_resolution)
+
+    def _fill_dem_slot(self, batch, slot, Z):
+        """One entry of run_batch's `dems` into the batch's DEM slot: an array (uploaded), or a
+        scene.CraterField, built on the device on the engine's grid."""
+        if isinstance(Z, scene.CraterField):
+            batch.build_dem(slot, Z, self.surface.half_width, base=Z.base)
+            return
+        Z = np.asarray(Z, np.float32)
+        batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
 
     def _fill_costmap_slot(self, batch, slot, cm):
         """One entry of run_batch's `costmaps` into the batch's costmap slot: an array, or a rock list
@@ -511,8 +537,7 @@ class MPPI_Controller:
             if variants:
                 batch.set_variants(variants)
             for slot, Z in enumerate(dems or []):
-                Z = np.asarray(Z, np.float32)
-                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
+                self._fill_dem_slot(batch, slot, Z)
             for slot, cm in enumerate(costmaps or []):
                 self._fill_costmap_slot(batch, slot, cm)
             for e in range(E):
@@ -559,7 +584,8 @@ class MPPI_Controller:
         weights) or a yardstick (variant or dict): every executed path is scored on the device with
         that one cost function (mppi_batch_score), each on its own episode's costmap.
 
-        dems: DEMs of the surface's shape, costmaps: costmaps of the surface's costmap shape (2-D, or
+        dems: DEMs of the surface's shape, or scene.CraterField values, built on the device on the
+        surface's grid (mppi_batch_build_dem: a Monte-Carlo over crater fields uploads no terrain); costmaps: costmaps of the surface's costmap shape (2-D, or
         flat as costmap_wp) or rock lists, built on the device as Surface.create_obstacles_costmap
         builds them ([[x, y, r], ...] about the origin (0, 0), or dict(obstacles=..., origin=(x, y)));
         they fill the batch's scene slots in list order.  episode_dem[e] / episode_costmap[e]: the
@@ -632,8 +658,7 @@ class MPPI_Controller:
             if variants:
                 batch.set_variants(variants)
             for slot, Z in enumerate(dems or []):
-                Z = np.asarray(Z, np.float32)
-                batch.set_dem(slot, Z.reshape(self.engine.dem_shape) if Z.ndim == 1 else Z)
+                self._fill_dem_slot(batch, slot, Z)
             for slot, cm in enumerate(costmaps or []):
                 self._fill_costmap_slot(batch, slot, cm)
             batch.set_tasks([_lib.make_task(_lib.make_state(starts[i, 0], starts[i, 1], headings[i], 0.0, 0.0,

@@ -47,6 +47,76 @@ def crater_dem(grid_size, half_width, bumps=BUMPS_9, scale=1.0):
     return Z.astype(np.float32)
 
 
+def crater_rows(bumps):
+    """Crater list -> contiguous float64 [n, 4] rows (cx, cy, height, width); n may be 0.  Accepted: the
+    reference's own shape [((cx, cy), height, width), ...] (MPPI_isaac.py:318), an (n, 4) array, or a
+    CraterField."""
+    if isinstance(bumps, CraterField):
+        return bumps.rows
+    if isinstance(bumps, np.ndarray):
+        a = np.asarray(bumps, np.float64)
+        if a.size and (a.ndim != 2 or a.shape[1] != 4):
+            raise ValueError(f"craters: an array must be (n, 4) rows (cx, cy, height, width), got {a.shape}")
+        return np.ascontiguousarray(a.reshape(-1, 4))
+    rows = []
+    for k, b in enumerate(bumps):
+        if len(b) == 3 and np.ndim(b[0]) == 1:
+            (cx, cy), h, w = b
+        elif len(b) == 4:
+            cx, cy, h, w = b
+        else:
+            raise ValueError(f"crater {k}: expected ((cx, cy), height, width) or (cx, cy, height, width), got {b!r}")
+        rows.append((float(cx), float(cy), float(h), float(w)))
+    return np.ascontiguousarray(np.asarray(rows, np.float64).reshape(-1, 4))
+
+
+class CraterField:
+    """A crater field as a value: the rows (cx, cy, height, width) and an optional base terrain
+    (float32 heights the craters are added to).  Wherever the controller takes a DEM array it takes
+    one of these and builds the heights on the device (Engine.build_dem / Batch.build_dem)."""
+
+    def __init__(self, bumps, base=None):
+        self.rows = crater_rows(bumps)
+        self.base = None if base is None else np.ascontiguousarray(base, dtype=np.float32)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def __repr__(self):
+        return f"CraterField({len(self)} craters{'' if self.base is None else ', base ' + str(self.base.shape)})"
+
+    def dem(self, grid_size, half_width):
+        """The heights on the host (crater_dem_separable)."""
+        return crater_dem_separable(grid_size, half_width, self.rows, self.base)
+
+
+def crater_dem_separable(grid_size, half_width, bumps, base=None):
+    """Surface.create_surface (MPPI_isaac.py:307-320) as the separable float64 sum the device builder
+    computes: x = linspace(-hw, hw, grid), row i at y_i = x_i; per crater the terms
+    (a, s) = (height - 0.5, 2 width^2) and (-(height + 0.5), 2 (width/2)^2); R[i, t] = a_t exp(-((y_i -
+    cy_t)^2) / s_t), C[t, j] = exp(-((x_j - cx_t)^2) / s_t); Z = R @ C in float64, plus the float32 base
+    widened to float64, rounded once to float32.  No crater is culled.  The CPU yardstick of
+    mppi_build_dem; not bitwise crater_dem (exp of a sum against a product of exps, the order of the sum)."""
+    grid_size = int(grid_size)
+    rows = crater_rows(bumps)
+    x = np.linspace(-half_width, half_width, grid_size)
+    Z = np.zeros((grid_size, grid_size), np.float64)
+    if rows.shape[0]:
+        cx, cy, h, w = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
+        a = np.stack([h - 0.5, -(h + 0.5)], 1).reshape(-1)                 # [2n] rim, bowl per crater
+        s = np.stack([2 * w ** 2, 2 * (w / 2) ** 2], 1).reshape(-1)
+        cx2, cy2 = np.repeat(cx, 2), np.repeat(cy, 2)
+        R = a[None, :] * np.exp(-((x[:, None] - cy2[None, :]) ** 2) / s[None, :])   # [grid, 2n]
+        Cf = np.exp(-((x[None, :] - cx2[:, None]) ** 2) / s[:, None])               # [2n, grid]
+        Z = R @ Cf
+    if base is not None:
+        base = np.asarray(base, np.float32)
+        if base.shape != Z.shape:
+            raise ValueError(f"base: shape {base.shape}, the DEM's is {Z.shape}")
+        Z = Z + base.astype(np.float64)
+    return Z.astype(np.float32)
+
+
 def random_obstacles(n=750, seed=99, extent=50.0, r_max=0.4):
     """MPPI_OO_current.py:721-725: [x, y, r] with RandomState(seed)."""
     rng = np.random.RandomState(seed)

@@ -180,6 +180,44 @@ int mppi_costmap_builder_build(mppi_costmap_builder* b, const double* obstacles,
 /* Device time (HIP events) of the builder's last build, in milliseconds. */
 int mppi_costmap_builder_last_ms(mppi_costmap_builder* b, double* ms);
 
+/* ---- on-device crater-field DEM ----
+ * Surface.create_surface(bumps) (MPPI_isaac.py:307-356) on the GPU.  craters: n rows of
+ * (cx, cy, height, width) float64, host memory: bump_center, bump_height, bump_width of the
+ * reference's list.  The grid is X, Y = meshgrid(linspace(-half_width, half_width, grid_size))
+ * (float64: x_j = j * step + (-half_width), step = 2 half_width / (grid_size - 1), the last point
+ * half_width itself; row i of the array lies at y_i = x_i).  Each crater is the two gaussians of
+ * :319-320, (height - 0.5) exp(-r2 / (2 width^2)) - (height + 0.5) exp(-r2 / (2 (width/2)^2)),
+ * each evaluated as the product exp(-(y_i - cy)^2 / s) exp(-(x_j - cx)^2 / s) of a row and a column
+ * factor, so the field is one [grid x 2n] . [2n x grid] float64 product (no crater is culled; the
+ * order of the sum is the kernel's).  base_host, if given, is added in float64; the sum is rounded
+ * once to float32.  n = 0 gives the base, or zeros.  Not bitwise the reference (its exp of the sum,
+ * its crater order): at most one float32 ulp apart, on about one cell in 10^5.
+ * MPPI_EINVAL, naming the crater and the field, for a non-finite cx, cy, height or width, a zero
+ * width (or one whose square under- or overflows), grid_size < 2 (or above 32768), and a half_width
+ * that is not finite and > 0.  All calls are synchronous. */
+enum mppi_dem_variant { MPPI_DEM_MFMA = 0, MPPI_DEM_VALU = 1 };  /* same result up to the summation order */
+typedef struct mppi_dem_builder mppi_dem_builder;
+int  mppi_dem_builder_create(int32_t device, mppi_dem_builder** out);
+void mppi_dem_builder_destroy(mppi_dem_builder* b);
+/* craters: n rows of (cx, cy, height, width) float64, host.  base_host: NULL or [grid*grid] float32.
+ * out_host / out_device [grid*grid] float32, either may be NULL. */
+int  mppi_dem_builder_build(mppi_dem_builder* b, const double* craters, int32_t n, int32_t grid_size,
+                            double half_width, const float* base_host, float* out_host, float* out_device,
+                            int32_t variant);
+int  mppi_dem_builder_last_ms(mppi_dem_builder* b, double* ms);   /* HIP events, factor + product */
+/* Test hook: the product kernel alone on factor tables the caller supplies in device memory, both
+ * term-major [terms][grid_size] float64 (r_dev[t][i] the row factors, c_dev[t][j] the column
+ * factors), terms a multiple of 4: out[i][j] = float32(sum_t r_dev[t][i] c_dev[t][j]).  With
+ * integer-valued factors every entry is exact, which pins the MFMA lane maps. */
+int  mppi_dem_builder_product(mppi_dem_builder* b, const double* r_dev, const double* c_dev, int32_t terms,
+                              int32_t grid_size, float* out_host, float* out_device, int32_t variant);
+/* create_surface + mppi_set_dem without the host round trip: builds into the context's own DEM buffer with
+ * rows = cols = grid_size, x_min = y_min = -(float)half_width, resolution = (float)(2*half_width/grid_size)
+ * (MPPI_isaac.py:265, :560-564), then the normal table and the verified reciprocal, as mppi_set_dem.
+ * A DEM borrowed by mppi_set_dem_device is let go of, not written into. */
+int  mppi_build_dem(mppi_ctx* ctx, const double* craters, int32_t n, int32_t grid_size, double half_width,
+                    const float* base_host, float* out_host, int32_t variant);
+
 /* reset("controller") (MPPI_isaac.py:489-497) + the robot/goal/sigma fields MPPI_step reads. */
 int mppi_set_state(mppi_ctx* ctx, const mppi_state* state);
 
@@ -417,6 +455,12 @@ int  mppi_batch_set_costmap(mppi_batch* b, int32_t slot, const float* cm_host);
 int  mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacles, int32_t n,
                               double origin_x, double origin_y, double r_robot, int32_t power,
                               int32_t metric, float* out_host);
+/* mppi_build_dem into DEM slot `slot`, with the context DEM's geometry: the context's DEM must be square
+ * with x_min = y_min = -(float)half_width and resolution (float)(2*half_width/rows) (MPPI_EINVAL
+ * otherwise); MPPI_ESTATE without a context DEM.  Everything else as mppi_batch_set_dem (replacing a
+ * live slot, an allocation failure leaves slot and batch as they were).  out_host may be NULL. */
+int  mppi_batch_build_dem(mppi_batch* b, int32_t slot, const double* craters, int32_t n, double half_width,
+                          const float* base_host, float* out_host, int32_t variant);
 int  mppi_batch_set_episode_scene(mppi_batch* b, int32_t e, int32_t dem_slot, int32_t costmap_slot);
 int  mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_trajectories);
 

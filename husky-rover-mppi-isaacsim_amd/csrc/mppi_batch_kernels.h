@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b
 // table (BatchArgs::scene) the episode's K and, where it holds slots, its DEM, normal table and
 // costmap replace the launch's; the grid is the context's, and a leaf block past the episode's
 // ceil(K / 256) returns first of all.
-template <int PROJ>
+// ALT: the critic set is a run-time value, per episode (the row of BatchArgs::crit behind the
+// episode's variant, else the launch's); false: no row is set and the context's set is the default,
+// and the kernel is the one it was before there was a choice (roles_body's ALT).
+template <int PROJ, bool ALT>
 __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const RolloutArgs a_in, const BatchArgs b) {
   const int e = blockIdx.y;
   // (null: no episode holds a scene slot or a K of its own) a leaf block beyond the episode's K
@@ -75,6 +78,15 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
       a.T = v->T;  // leaf_records (its dense / sparse forecast included) reads a.T only
       a.fk = v->fk;
       a.fa = v->fa;
+      if constexpr (ALT) {
+        if (b.crit) {  // the row's critic set (slope_mode -1: none given, the context's stays)
+          const BatchCriticRow cr = b.crit[vi];
+          if (cr.slope_mode >= 0) {
+            a.slope_body = cr.slope_mode;
+            a.w_orient = cr.w_orient;
+          }
+        }
+      }
     } else if (b.proj != PROJ) {
       return;
     }
@@ -103,7 +115,7 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
   a.u_nom2 = unom + H;
   a.cost_out = b.cost + (size_t)e * b.k_pad;
   a.nodes = b.nodes + (size_t)e * b.blocks * (2 * H + 2);
-  roles_body<256, PROJ, 0, false, false>(a, (int)blockIdx.x, nullptr);
+  roles_body<256, PROJ, 0, false, false, ALT>(a, (int)blockIdx.x, nullptr);
 }
 
 // The critics' scalar parts of an episode at (x, y) with the goal (gx, gy): state_fields() of
@@ -476,10 +488,15 @@ hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t 
 
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj) {
   const dim3 g((unsigned)b.blocks, (unsigned)b.E), t(NROLES * 256);
-  if (proj == 3)
-    hipLaunchKernelGGL(mppi_batch_rollout_kernel<3>, g, t, lds, st, a, b);
-  else
-    hipLaunchKernelGGL(mppi_batch_rollout_kernel<2>, g, t, lds, st, a, b);
+  // (a batch with no critic row on a context with the default set runs the form compiled without the choice)
+  const bool alt = b.crit != nullptr || a.slope_body || a.w_orient != 0.0f;
+  if (proj == 3) {
+    if (alt) hipLaunchKernelGGL((mppi_batch_rollout_kernel<3, true>), g, t, lds, st, a, b);
+    else hipLaunchKernelGGL((mppi_batch_rollout_kernel<3, false>), g, t, lds, st, a, b);
+  } else {
+    if (alt) hipLaunchKernelGGL((mppi_batch_rollout_kernel<2, true>), g, t, lds, st, a, b);
+    else hipLaunchKernelGGL((mppi_batch_rollout_kernel<2, false>), g, t, lds, st, a, b);
+  }
   return hipGetLastError();
 }
 

@@ -179,6 +179,15 @@ void state_fields(const mppi_params& p, const mppi_state& st, ServerCmd& d) {
   d.speed_on = (dist < 2.0f) ? 0 : 1;
 }
 
+std::string critics_error(const mppi_critics& k, int H) {
+  if (k.slope_mode != MPPI_SLOPE_WHEELS && k.slope_mode != MPPI_SLOPE_BODY)
+    return "slope_mode must be MPPI_SLOPE_WHEELS (0) or MPPI_SLOPE_BODY (1), got " + std::to_string(k.slope_mode);
+  if (!std::isfinite(k.w_orientation)) return "w_orientation must be finite";
+  if (k.w_orientation != 0.0f && H < 2)
+    return "w_orientation != 0 needs num_iterations >= 2 (the rollout's last displacement)";
+  return std::string();
+}
+
 void fill_rollout(const mppi_ctx* c, const Plan& pl, const mppi_state& st, uint64_t step,
                   const float* unom, RolloutArgs& a) {
   const mppi_params& p = c->p;
@@ -242,6 +251,8 @@ void fill_rollout(const mppi_ctx* c, const Plan& pl, const mppi_state& st, uint6
   a.w_slope = p.w_slope;
   a.w_speed = p.w_speed;
   a.w_obs = p.w_obstacle;
+  a.slope_body = c->crit.slope_mode == MPPI_SLOPE_BODY;
+  a.w_orient = c->crit.w_orientation;
   a.thr = p.collision_threshold;
   a.pen = p.collision_penalty;
   a.T = p.temperature;
@@ -1381,6 +1392,21 @@ int mppi_get_costs(mppi_ctx* c, float* costs, int64_t n) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(costs, c->sb.cost, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_set_critics(mppi_ctx* c, const mppi_critics* k) {
+  if (!c || !k) return fail(MPPI_EINVAL, "null argument");
+  if (int rc_q = quiesce(c)) return rc_q;  // the next server launch carries the set
+  const std::string err = critics_error(*k, H_of(c));
+  if (!err.empty()) return fail(MPPI_EINVAL, "set_critics: " + err);
+  c->crit = *k;
+  return MPPI_OK;
+}
+
+int mppi_get_critics(mppi_ctx* c, mppi_critics* out) {
+  if (!c || !out) return fail(MPPI_EINVAL, "null argument");
+  *out = c->crit;
   return MPPI_OK;
 }
 

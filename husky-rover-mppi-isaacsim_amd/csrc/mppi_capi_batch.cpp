@@ -46,6 +46,9 @@ struct mppi_batch {
   std::vector<int> ep_var;                   // [E] each episode's row, -1: none
   DeviceBuf<BatchVariant> d_var;             // [kBatchMaxVariants]
   DeviceBuf<int> d_ep_var;                   // [E]
+  // the variant rows' critic sets (mppi_batch_set_variant_critics): row i belongs to variant row i
+  std::vector<mppi_critics> critics;         // as last set
+  DeviceBuf<BatchCriticRow> d_crit;          // [kBatchMaxVariants], rows past the set: slope_mode -1
   // [E] x, y, goal_x, goal_y of each episode when its most recent run began (mppi_batch_score)
   std::vector<std::array<float, 4>> origin;
   // per-episode scenes and trajectory counts (mppi_batch_set_dem / _set_costmap / _set_episode_scene /
@@ -68,6 +71,7 @@ struct mppi_batch {
   enum Campaign { kNotStarted, kUnfinished, kComplete } campaign = kNotStarted;
 };
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
+static_assert(sizeof(mppi_critics) == sizeof(BatchCriticRow), "mppi_critics layout");
 static_assert(sizeof(SceneRecord) == sizeof(BatchScene), "SceneRecord is BatchScene field for field");
 
 namespace {
@@ -230,6 +234,7 @@ BatchArgs batch_args(mppi_batch* b, int proj, const mppi_loop_policy& pol) {
   z.horizon = c->p.horizon;
   z.rwheel = c->p.robot_radius;
   z.active_count = b->active_count;
+  z.crit = b->critics.empty() ? nullptr : b->d_crit.get();  // (read behind a variant index only)
   return z;
 }
 
@@ -518,7 +523,7 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
   const mppi_params& p = c->p;
   const size_t E = goals.size();
   // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps][base rows]
-  const size_t bg = E * sizeof(ScoreGoal), bn = up16(E * 4), bt = E * 16, bp = up16(cmaps.size() * sizeof(float*)),
+  const size_t bg = up16(E * sizeof(ScoreGoal)), bn = up16(E * 4), bt = E * 16, bp = up16(cmaps.size() * sizeof(float*)),
                bb = base_rows.size() * sizeof(int64_t);
   DeviceBuf<char> dbuf;
   HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp + bb));
@@ -550,12 +555,13 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
   a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
   a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
   a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  a.w_orient = c->crit.w_orientation;  // the context's set; a log is a body path in either slope mode
   a.cost = d_cost;
   a.terms = d_terms;
   a.collisions = d_col;
   a.cm_path = bp ? d_cmaps : nullptr;
   a.base_row = bb ? d_base : nullptr;
-  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), bg, hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(d_goals, goals.data(), E * sizeof(ScoreGoal), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && bp)
     e = hipMemcpyAsync(d_cmaps, cmaps.data(), cmaps.size() * sizeof(float*), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && bb) e = hipMemcpyAsync(d_base, base_rows.data(), bb, hipMemcpyHostToDevice, c->stream);
@@ -841,6 +847,32 @@ int mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant* 
   return MPPI_OK;
 }
 
+int mppi_batch_set_variant_critics(mppi_batch* b, int32_t n, const mppi_critics* rows) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (n < 0 || n > kBatchMaxVariants)
+    return fail(MPPI_EINVAL, "batch: need 0 <= n <= " + std::to_string(kBatchMaxVariants) + " critic rows");
+  if (n > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  for (int i = 0; i < n; ++i) {
+    const std::string err = critics_error(rows[i], b->H);
+    if (!err.empty()) return fail(MPPI_EINVAL, "batch: critic row " + std::to_string(i) + ": " + err);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (no run of the batch is in flight: every call waits)
+  if (n > 0) {
+    if (!b->d_crit && b->d_crit.alloc(kBatchMaxVariants * sizeof(BatchCriticRow)))
+      return fail(MPPI_EHIP, "batch: critic table allocation failed");
+    std::vector<BatchCriticRow> tab(kBatchMaxVariants, BatchCriticRow{-1, 0.0f});
+    for (int i = 0; i < n; ++i) tab[i] = BatchCriticRow{rows[i].slope_mode, rows[i].w_orientation};
+    HIP_TRY(hipMemcpyAsync(b->d_crit, tab.data(), tab.size() * sizeof(BatchCriticRow), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  b->critics.assign(rows, rows + n);
+  return MPPI_OK;
+}
+
 int mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant) {
   if (int rc = batch_episode(b, e)) return rc;
   if (variant < -1 || variant >= (int32_t)b->variants.size())
@@ -1014,7 +1046,7 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
     }
     ServerCmd d;
     state_fields(p, st, d);
-    goals[e] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
+    goals[e] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, d.x0, d.y0, 0};
   }
   // each path on its episode's costmap: the slot's where the episode holds one, else the context's
   // (no array at all while no episode in use holds a costmap slot)
@@ -1205,7 +1237,7 @@ int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, c
     st.goal_y = o.goal_y;
     ServerCmd d;
     state_fields(c->p, st, d);
-    goals[i] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, 0};
+    goals[i] = ScoreGoal{d.gx, d.gy, d.igx, d.igy, d.pf_scale, d.pf_far, d.speed_on, d.x0, d.y0, 0};
     base[i] = b->tbook.base((int)i);
   }
   // each path on its task's costmap (no array at all while no listed task holds a costmap slot)

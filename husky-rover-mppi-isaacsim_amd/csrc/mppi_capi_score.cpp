@@ -3,6 +3,7 @@
 
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "mppi.h"
 #include "mppi_ctx.h"
@@ -40,15 +41,21 @@ namespace {
 // costmap and critic parameters; the kernel is bracketed by HIP events (score_ms).  Waits for the stream.
 int score_device(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* lengths, const float* traj,
                  const float* lw, const float* rw, const float* v, const mppi_state& st, float* cost,
-                 float* terms, int32_t* collisions) {
+                 float* terms, int32_t* collisions, float* orient = nullptr) {
   const mppi_params& p = c->p;
   ServerCmd d;
   state_fields(p, st, d);
   ScoreArgs a;
   std::memset(&a, 0, sizeof(a));
   a.traj = traj;
-  a.lw = lw;
-  a.rw = rw;
+  // the critic set's slope mode: the body form is the kernel without wheel arrays
+  const bool body = c->crit.slope_mode == MPPI_SLOPE_BODY;
+  a.lw = body ? nullptr : lw;
+  a.rw = body ? nullptr : rw;
+  a.w_orient = c->crit.w_orientation;
+  a.x0 = d.x0;
+  a.y0 = d.y0;
+  a.orient = orient;
   a.v = v;
   a.lengths = lengths;
   a.n = n;
@@ -145,7 +152,12 @@ int mppi_score_paths(mppi_ctx* c, int64_t n, int32_t stride, const int32_t* leng
   return MPPI_OK;
 }
 
-int mppi_get_cost_terms(mppi_ctx* c, float* terms, int32_t* collisions) {
+}  // extern "C"
+
+namespace {
+
+// mppi_get_cost_terms (orient == false: terms [K*4]) and mppi_get_cost_terms5 (terms [K*5])
+int cost_terms(mppi_ctx* c, float* terms, int32_t* collisions, bool orient) {
   if (!c) return fail(MPPI_EINVAL, "null context");
   if (int rc_q = quiesce(c)) return rc_q;
   int rc = check_ready(c);
@@ -159,9 +171,15 @@ int mppi_get_cost_terms(mppi_ctx* c, float* terms, int32_t* collisions) {
   // device-side dump buffers for traj, lw, rw, v only, and the 20 bytes per trajectory that leave
   DeviceBuf<float> dev[4];
   const size_t cnt[4] = {3 * KH, 3 * KH, 3 * KH, KH};
-  DeviceBuf<float> d_terms;
+  DeviceBuf<float> d_terms, d_po;
   DeviceBuf<int32_t> d_col;
+  std::vector<float> t4, po;
   int out_rc = MPPI_OK;
+  if (orient) {
+    if (d_po.alloc((size_t)K * 4)) out_rc = fail(MPPI_EHIP, "cost_terms allocation failed");
+    t4.resize((size_t)K * 4);
+    po.resize((size_t)K);
+  }
   for (int i = 0; i < 4 && out_rc == MPPI_OK; ++i)
     if (dev[i].alloc(cnt[i] * sizeof(float))) out_rc = fail(MPPI_EHIP, "cost_terms allocation failed");
   if (out_rc == MPPI_OK && (d_terms.alloc((size_t)K * 16) || d_col.alloc((size_t)K * 4)))
@@ -177,16 +195,38 @@ int mppi_get_cost_terms(mppi_ctx* c, float* terms, int32_t* collisions) {
     out_rc = enqueue_rollout(c, c->last.proj, c->last.step, c->last.mode, c->last.plan,
                              c->sb.u_nom[c->last.nominal], c->last.state, &d);
     if (out_rc == MPPI_OK)
-      out_rc = score_device(c, K, H, nullptr, dev[0], dev[1], dev[2], dev[3], c->last.state, nullptr, d_terms, d_col);
+      out_rc = score_device(c, K, H, nullptr, dev[0], dev[1], dev[2], dev[3], c->last.state, nullptr, d_terms, d_col,
+                            orient ? d_po.get() : nullptr);
     if (out_rc == MPPI_OK && terms &&
-        hipMemcpyAsync(terms, d_terms, (size_t)K * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        hipMemcpyAsync(orient ? t4.data() : terms, d_terms, (size_t)K * 16, hipMemcpyDeviceToHost, c->stream) !=
+            hipSuccess)
+      out_rc = fail(MPPI_EHIP, "cost_terms copy failed");
+    if (out_rc == MPPI_OK && terms && orient &&
+        hipMemcpyAsync(po.data(), d_po, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
       out_rc = fail(MPPI_EHIP, "cost_terms copy failed");
     if (out_rc == MPPI_OK && collisions &&
         hipMemcpyAsync(collisions, d_col, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
       out_rc = fail(MPPI_EHIP, "cost_terms copy failed");
     if (out_rc == MPPI_OK && hipStreamSynchronize(c->stream) != hipSuccess) out_rc = fail(MPPI_EHIP, "cost_terms sync failed");
+    if (out_rc == MPPI_OK && terms && orient)
+      for (int64_t k = 0; k < K; ++k) {
+        std::memcpy(terms + 5 * k, t4.data() + 4 * k, 16);
+        terms[5 * k + 4] = po[(size_t)k];
+      }
   }
   return out_rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mppi_get_cost_terms(mppi_ctx* c, float* terms, int32_t* collisions) {
+  return cost_terms(c, terms, collisions, false);
+}
+
+int mppi_get_cost_terms5(mppi_ctx* c, float* terms5, int32_t* collisions) {
+  return cost_terms(c, terms5, collisions, true);
 }
 
 int mppi_get_score_ms(mppi_ctx* c, double* ms) {

@@ -257,6 +257,7 @@ struct LastStep {
 
 struct mppi_ctx {
   mppi_params p{};
+  mppi_critics crit{MPPI_SLOPE_WHEELS, 0.0f};  // the critic set (mppi_set_critics)
   int device = 0;
   mppi::Stream stream;  // owned, or the caller's (mppi_set_stream)
   int prio_least = 0, prio_greatest = 0;
@@ -302,6 +303,8 @@ int grow(DeviceBuf<T>& b, size_t bytes, hipStream_t st) {
 int check_ready(mppi_ctx* c);
 Plan make_plan(const mppi_ctx* c);
 int quiesce(mppi_ctx* c);
+// empty when the set is valid for a context of H steps, else the message naming the field
+std::string critics_error(const mppi_critics& k, int H);
 int verified_reciprocal(mppi_ctx* c, float b, float* y_out);
 void state_fields(const mppi_params& p, const mppi_state& st, ServerCmd& d);
 void fill_rollout(const mppi_ctx* c, const Plan& pl, const mppi_state& st, uint64_t step, const float* unom,

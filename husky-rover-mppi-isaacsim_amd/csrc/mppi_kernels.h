@@ -55,11 +55,18 @@ struct RolloutArgs {
   int64_t K;         // trajectories in this launch (shard-local)
   int64_t k_offset;  // global index of trajectory 0 (Philox subsequence)
   int H;
+  // The critic set (mppi_set_critics) fills the two alignment holes of this block, here and behind
+  // `res`, so that no other field's offset moved when it came (the server's argument loads and with
+  // them its register allocation stayed what they were).  slope_body: the slope critic on the body
+  // path (_avoid_slope, critics_warp.py:131-166: both "wheels" of slope_term on the bilinear body
+  // height) instead of the wheel contacts.
+  int slope_body;
   // DEM
   const float* Z;
   const float4* ntab;  // per-cell normals [(rows+1) x (grid+1)] (mppi_normal_table_kernel)
   int rows, grid;
   float x_min, y_min, res;
+  float w_orient;  // the critic set: weight of _path_orientation_critic (:44-82; 0: the term does not exist)
   // costmap
   const float* cm;
   int cm_size;
@@ -218,6 +225,14 @@ struct BatchVariant {
 };
 static_assert(sizeof(BatchVariant) == 56, "BatchVariant layout");
 constexpr int kBatchMaxVariants = 1024;
+// One row of the batch's critic table: mppi_critics (include/mppi.h) field for field.  Row i belongs to
+// variant row i; the rows the caller did not give hold slope_mode -1: the context's set, which the
+// launch's arguments carry.
+struct BatchCriticRow {
+  int slope_mode;
+  float w_orient;
+};
+static_assert(sizeof(BatchCriticRow) == 8, "BatchCriticRow layout");
 // Per-episode scene and trajectory count (mppi_batch_set_dem / _set_costmap / _set_episode_scene /
 // _set_episode_trajectories).  One record per episode, read as one wave-uniform 16-byte load: its
 // DEM and costmap slots (-1: the context's) and its K with blocks = ceil(K / 256) (the context's for
@@ -259,9 +274,12 @@ struct BatchArgs {
   float sigma_base, sigma_div, goal_tol;  // mppi_loop_policy (an episode's variant overrides the sigmas)
   float horizon, rwheel;                  // mppi_params horizon, robot_radius
   int* active_count;                      // pinned host memory: episodes still active
+  // null while no critic rows are set (mppi_batch_set_variant_critics): [kBatchMaxVariants], read by
+  // the rollout only, behind the variant index it has loaded already
+  const BatchCriticRow* crit;
 };
 // (the scene pointer took the place of two paddings: the kernels' argument segment did not grow)
-static_assert(sizeof(BatchArgs) == 136, "BatchArgs layout");
+static_assert(sizeof(BatchArgs) == 144, "BatchArgs layout");
 constexpr int kBatchMaxRecords = 16;  // leaf records per episode: the finish's tree is one LDS pass
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st);
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);

@@ -623,6 +623,15 @@ __device__ __forceinline__ float slope_term(float plx, float ply, float plz, flo
   return (ls > rs) ? ls : rs;
 }
 
+// critics_warp.py:44-82 _path_orientation_critic: (xd, yd) robot -> goal, (x2, y2) the rollout's last
+// displacement X[H-1] - X[H-2]; 0 with the robot on the goal (DEFINED, DESIGN.md §4: the reference
+// divides 0 by 0 there).
+__device__ __forceinline__ float orientation_term(float xd, float yd, float x2, float y2) {
+  const float s = (xd * x2) + (yd * y2);
+  const float den = fabsf(xd) + fabsf(yd);
+  return (s <= 0.0f && den != 0.0f) ? (-s) / den : 0.0f;
+}
+
 // critics_warp.py:244-248 costmap index (clamped, DEFINED)
 template <bool F>
 __device__ __forceinline__ int costmap_index(int size, float hw, const Recip& rres_c, float x,
@@ -1428,6 +1437,7 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
     }
   }
   float pf_sum = 0.f, sw = 0.f, sp = 0.f, ob = 0.f, last_x = a.x0, last_y = a.y0;
+  float prev_x = a.x0, prev_y = a.y0;  // the step before last_x / last_y (the orientation critic)
   float lwx = 0.f, lwy = 0.f, lwz = 0.f, rwx = 0.f, rwy = 0.f, rwz = 0.f;
   float* ust = a.ustore + (size_t)blockIdx.x * (2 * H) * TB + tj;
 
@@ -1524,6 +1534,12 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
     // PROD / CONS: the half produces step p / consumes step sc = p - PAIR_LAG for sure
     // (no runtime test: branch-free loads let the compiler count vmcnt exactly); with
     // neither set, both are tested at run time (the few halves at the ends).
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    // BODY (RolloutArgs::slope_body, uniform): the whole loop twice, so that the wheels form keeps its
+    // instruction stream, with no merge of a height in flight and a computed one
+    auto side_wave = [&](auto body_tag) __attribute__((always_inline)) {
+    constexpr bool BODY = decltype(body_tag)::value;
     auto half = [&](auto odd_tag, auto prod_tag, auto cons_tag, int p, float& e1r, float& e2r,
                     float& cm_mine, float& cm_prev) __attribute__((always_inline)) {
       constexpr bool ODD = decltype(odd_tag)::value;
@@ -1578,7 +1594,13 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
         const float x = ro[0], y = ro[TB], cx = ro[2 * TB], cy = ro[3 * TB];
         const float vq = ring_in[(sc % D) * RI * TB + tj];  // v of step sc (slot not reused yet)
         if constexpr (!ODD) {  // contacts of an even step: heights in flight until the odd half
-          if constexpr (PROJ == 3) {
+          if constexpr (BODY) {  // _avoid_slope (critics_warp.py:131-166): both "wheels" on the body point
+            float q[4];
+            dem.template corners<false>(x, y, q, nobad);
+            elx = erx = x;
+            ely = ery = y;
+            elz = erz = bilinear<false>(x, y, q, dem.template rr<false>(), nobad);
+          } else if constexpr (PROJ == 3) {
             elx = x + cx;
             ely = y + cy;
             elz = dem.template point<false>(elx, ely, nobad);
@@ -1592,6 +1614,8 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
         cm_mine = a.cm[costmap_index<false>(a.cm_size, a.hw, rcm, x, y, nobad, a.rinv_res_c, a.cdiv_res_c)];
         const float pft = pf_sum + 10.0f * (fabsf(x - a.gx) + fabsf(y - a.gy));
         pf_sum = (sc < H - 1) ? pft : pf_sum;   // _path_follow_critic sum over t < H-1
+        prev_x = last_x;
+        prev_y = last_y;
         last_x = x;
         last_y = y;
         if constexpr (ODD) {  // _avoid_slope_wheels term (i, i+2) of the even step i = sc - 1 < H-3
@@ -1609,7 +1633,7 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
         if constexpr (DUMP) {
           if (valid) {
             float lx = elx, ly = ely, lz = elz, rx = erx, ry = ery, rz = erz;
-            if (ODD) {
+            if (ODD || BODY) {  // (body mode: the even set holds the body point, not the contacts)
               lx = ly = lz = rx = ry = rz = 0.f;
               if constexpr (PROJ == 3) {
                 lx = x + cx;
@@ -1635,8 +1659,6 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
         e2r = eps_row[(size_t)(H + tn) * TB];
       }
     };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
     int p = 0;
     for (const int p1 = min(H, PAIR_LAG) & ~1; p < p1; p += 2) {  // produce only
       half(F_{}, T_{}, F_{}, p, eA1, eA2, cmA, cmB);
@@ -1652,6 +1674,9 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
       half(F_{}, F_{}, F_{}, p, eA1, eA2, cmA, cmB);
       if (p + 1 < H + PAIR_LAG) half(T_{}, F_{}, F_{}, p + 1, eB1, eB2, cmB, cmA);
     }
+    };
+    if (a.slope_body) side_wave(T_{});
+    else side_wave(F_{});
     const float cm_last = ((H - 1) & 1) ? cmB : cmA;
     if (cm_last > a.thr) ob = ob + a.pen;  // last step's obstacle term
     ob = ob + cm_last;
@@ -1664,6 +1689,8 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
       pf = pf_sum;
     }
     float cost = a.w_path * pf;
+    if (a.w_orient != 0.0f)  // the menu's first line, when it exists
+      cost = a.w_orient * orientation_term(a.gx - a.x0, a.gy - a.y0, last_x - prev_x, last_y - prev_y) + cost;
     cost = cost + a.w_slope * sw;
     cost = cost + a.w_speed * sp;
     cost = cost + a.w_obs * ob;
@@ -1711,7 +1738,13 @@ constexpr int ROLE_CHAIN = 0, ROLE_PROD = 1, ROLE_WHEEL = 2, ROLE_COST = 3, NROL
 
 // FUSED: returns the workgroup's ticket (its rank among the workgroups that have completed their
 // records, from the record counter rec_cnt); otherwise -1.
-template <int TB, int PROJ, int MODE, bool DUMP, bool FUSED>
+// ALT: the critic set (RolloutArgs::slope_body, w_orient) is read at run time, both wave-uniform (the
+// batch rollout, where it is per episode); false: the default set, compiled in.  The single-context
+// kernels instantiate both and launch the default form for the default set, so that form is the
+// code it was before there was a choice: the kernel sits at its SGPR limit, and even the cost wave's
+// few extra instructions moved constants out of scalar registers in the server's chain loop
+// (165 -> 167 instructions per step).
+template <int TB, int PROJ, int MODE, bool DUMP, bool FUSED, bool ALT = true>
 __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigned* rec_cnt, int* ticket_lds = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int NT = NROLES * TB;
@@ -1772,7 +1805,11 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
   };
   using T_ = std::true_type;
   using F_ = std::false_type;
-  float c_pf = 0.f, c_ob = 0.f;  // COST: the critic sums, kept across the barrier
+  // COST: the head of the cost (the weighted path-follow term, behind the orientation term when there
+  // is one) and the obstacle sum, kept across the barrier.  The head is formed before the barrier so
+  // that w_path and w_orient are not live across the other roles' loops: the kernel sits at its SGPR
+  // limit, and one more scalar live in the chain loop costs it rematerialised constants there.
+  float c_head = 0.f, c_ob = 0.f;
 
   if (role == ROLE_CHAIN) {
     // ---------------- the serial projection, one step per iteration
@@ -1918,6 +1955,10 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
     float sw = 0.f;
     float Alx = 0.f, Aly = 0.f, Alz = 0.f, Arx = 0.f, Ary = 0.f, Arz = 0.f;
     float Blx = 0.f, Bly = 0.f, Blz = 0.f, Brx = 0.f, Bry = 0.f, Brz = 0.f;
+    // BODY (uniform): with ALT the whole loop twice, selected before the first step, so that no
+    // height in flight is merged with a computed one
+    auto wheel_wave = [&](auto body_tag) __attribute__((always_inline)) {
+    constexpr bool BODY = decltype(body_tag)::value;
     auto contacts = [&](int sc, float& lx, float& ly, float& lz, float& rx, float& ry, float& rz)
         __attribute__((always_inline)) {
       wait_ge(f_chain, sc + 1, seen_chain);
@@ -1925,12 +1966,14 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
       const float x = ro[0], y = ro[TB], cx = ro[2 * TB], cy = ro[3 * TB];
       lx = ly = lz = rx = ry = rz = 0.f;
       if constexpr (PROJ == 3) {
-        lx = x + cx;
-        ly = y + cy;
-        lz = dem.template point<false>(lx, ly, nobad);
-        rx = x - cx;
-        ry = y - cy;
-        rz = dem.template point<false>(rx, ry, nobad);
+        if constexpr (DUMP || !BODY) {  // (the dump keeps the contacts in body mode)
+          lx = x + cx;
+          ly = y + cy;
+          lz = dem.template point<false>(lx, ly, nobad);
+          rx = x - cx;
+          ry = y - cy;
+          rz = dem.template point<false>(rx, ry, nobad);
+        }
       }
       if constexpr (DUMP) {
         if (valid) {
@@ -1938,6 +1981,14 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
           if (a.d_lw) { a.d_lw[o3] = lx; a.d_lw[o3 + 1] = ly; a.d_lw[o3 + 2] = lz; }
           if (a.d_rw) { a.d_rw[o3] = rx; a.d_rw[o3 + 1] = ry; a.d_rw[o3 + 2] = rz; }
         }
+      }
+      if constexpr (BODY) {  // _avoid_slope (critics_warp.py:131-166): both "wheels" on the body point,
+                             // its height the bilinear of projection_warp.py:318 / :378
+        float q[4];
+        dem.template corners<false>(x, y, q, nobad);
+        lx = rx = x;
+        ly = ry = y;
+        lz = rz = bilinear<false>(x, y, q, dem.template rr<false>(), nobad);
       }
     };
     // even step sc in set X (other set Y): the term of (sc - 4, sc - 2) = (X, Y), then X = sc
@@ -1982,11 +2033,19 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
           : slope_term<false>(Alx, Aly, Alz, Blx, Bly, Blz, Arx, Ary, Arz, Brx, Bry, Brz, nobad);
       sw = sw + term;
     }
+    };
+    if constexpr (ALT) {
+      if (a.slope_body) wheel_wave(T_{});
+      else wheel_wave(F_{});
+    } else {
+      wheel_wave(F_{});
+    }
     sw_lds[tj] = sw;
   } else {
     // ---------------- costmap gather (used one step later), path-follow, speed, obstacle
     int seen_chain = 0;
     float pf_sum = 0.f, ob = 0.f, last_x = a.x0, last_y = a.y0;
+    float prev_x = a.x0, prev_y = a.y0;  // the step before last_x / last_y (the orientation critic)
     float cmA = 0.f, cmB = 0.f;  // costmap value of the even / odd step
     Recip rcm;
     rcm.b = a.res_c;
@@ -1997,6 +2056,8 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
       cm_mine = a.cm[costmap_index<false>(a.cm_size, a.hw, rcm, x, y, nobad, a.rinv_res_c, a.cdiv_res_c)];
       const float pft = pf_sum + 10.0f * (fabsf(x - a.gx) + fabsf(y - a.gy));
       pf_sum = (sc < H - 1) ? pft : pf_sum;  // _path_follow_critic sum over t < H-1
+      prev_x = last_x;
+      prev_y = last_y;
       last_x = x;
       last_y = y;
       // _avoid_obstacle: the costmap value gathered one step earlier (step sc - 1)
@@ -2022,13 +2083,17 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
     } else {
       pf = pf_sum;
     }
-    c_pf = pf;
+    c_head = a.w_path * pf;  // critics_warp.py:324-325, this f32 add order
+    if constexpr (ALT) {
+      if (a.w_orient != 0.0f)  // the menu's first line, when it exists
+        c_head = a.w_orient * orientation_term(a.gx - a.x0, a.gy - a.y0, last_x - prev_x, last_y - prev_y) + c_head;
+    }
     c_ob = ob;
   }
   __syncthreads();  // WHEEL's slope sums are in sw_lds
   if (clk_wg) a.clk[5] = __builtin_amdgcn_s_memrealtime();  // every role of workgroup 0 done
-  if (role == ROLE_COST) {  // critics_warp.py:325-329, this f32 add order
-    float cost = a.w_path * c_pf;
+  if (role == ROLE_COST) {  // critics_warp.py:326-329, this f32 add order
+    float cost = c_head;
     cost = cost + a.w_slope * sw_lds[tj];
     cost = cost + a.w_speed * cost_lds[tj];  // (the producer's speed critic sum)
     cost = cost + a.w_obs * c_ob;
@@ -2058,12 +2123,12 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
 
 // One workgroup per CU at most: a grid smaller than the blocks runs them in turn (block blockIdx.x,
 // + gridDim.x, ...), each a whole role-split rollout and leaf record.
-template <int TB, int PROJ, int MODE, bool DUMP>
+template <int TB, int PROJ, int MODE, bool DUMP, bool ALT>
 __global__ __launch_bounds__(NROLES * TB) void mppi_rollout_roles_kernel(const RolloutArgs a_in) {
   RolloutArgs a = a_in;
   const int nblk = (int)((a.K + TB - 1) / TB);
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    roles_body<TB, PROJ, MODE, DUMP, false>(a, blk, nullptr);
+    roles_body<TB, PROJ, MODE, DUMP, false, ALT>(a, blk, nullptr);
     if (blk + (int)gridDim.x < nblk) __syncthreads();  // (the next block reuses the LDS)
   }
 }
@@ -3487,17 +3552,22 @@ template <int TB, int PROJ>
 static hipError_t launch_roles_m(const RolloutArgs& a, int blocks, size_t lds, hipStream_t st, int mode,
                                  bool dump) {
   const dim3 g(blocks), b(NROLES * TB);
-  if (mode == 0) {
-    if (dump)
-      hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 0, true>), g, b, lds, st, a);
-    else
-      hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 0, false>), g, b, lds, st, a);
-  } else {
-    if (dump)
-      hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 1, true>), g, b, lds, st, a);
-    else
-      hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 1, false>), g, b, lds, st, a);
-  }
+  auto launch = [&](auto alt_tag) {  // (the default critic set runs the form compiled without the choice)
+    constexpr bool ALT = decltype(alt_tag)::value;
+    if (mode == 0) {
+      if (dump)
+        hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 0, true, ALT>), g, b, lds, st, a);
+      else
+        hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 0, false, ALT>), g, b, lds, st, a);
+    } else {
+      if (dump)
+        hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 1, true, ALT>), g, b, lds, st, a);
+      else
+        hipLaunchKernelGGL((mppi_rollout_roles_kernel<TB, PROJ, 1, false, ALT>), g, b, lds, st, a);
+    }
+  };
+  if (a.slope_body || a.w_orient != 0.0f) launch(std::true_type{});
+  else launch(std::false_type{});
   return hipGetLastError();
 }
 
@@ -3625,7 +3695,7 @@ __device__ __forceinline__ const ServerLaunch* fresh_args() {
 // for the server's idle exit on every step: 359 launches instead of 3 for 220 steps and half the
 // headline (profiles/leaf_sparse_notes.md).  The cap costs one dword spilled at entry and reloaded
 // once per step, outside the rollout.
-template <int TB, int PROJ>
+template <int TB, int PROJ, bool ALT>
 __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) void mppi_step_server_kernel(
     const ServerLaunch args) {
   __shared__ unsigned cmd_lds[32];
@@ -3739,7 +3809,7 @@ __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) v
     const int64_t W = 4 * (int64_t)z.nroll * ((a.H + 1) >> 1);
     const int nn = z.nroll - z.fin_groups;
     const int64_t S = 2 * (int64_t)nn + z.fin_groups - 1;
-    const int ticket = roles_body<TB, PROJ, 0, false, true>(a, (int)blockIdx.x, z.rec_cnt, sh);
+    const int ticket = roles_body<TB, PROJ, 0, false, true, ALT>(a, (int)blockIdx.x, z.rec_cnt, sh);
     if (ticket == z.nroll - 1 && tid == 0 && z.clk) {  // the rollout's time on the server, summed
       const uint64_t now = __builtin_amdgcn_s_memrealtime();
       z.clk[kClkServer + 8 * (seq & 7) + 1] = now;
@@ -3830,10 +3900,15 @@ __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) v
 
 hipError_t launch_step_server(const RolloutArgs& a, const ServerArgs& z, size_t lds, hipStream_t st, int proj) {
   const dim3 g((unsigned)z.nroll), b(NROLES * 256);
-  if (proj == 3)
-    hipLaunchKernelGGL((mppi_step_server_kernel<256, 3>), g, b, lds, st, ServerLaunch{a, z});
-  else
-    hipLaunchKernelGGL((mppi_step_server_kernel<256, 2>), g, b, lds, st, ServerLaunch{a, z});
+  // (the launch's critic set is fixed: mppi_set_critics stops the server)
+  const bool alt = a.slope_body || a.w_orient != 0.0f;
+  if (proj == 3) {
+    if (alt) hipLaunchKernelGGL((mppi_step_server_kernel<256, 3, true>), g, b, lds, st, ServerLaunch{a, z});
+    else hipLaunchKernelGGL((mppi_step_server_kernel<256, 3, false>), g, b, lds, st, ServerLaunch{a, z});
+  } else {
+    if (alt) hipLaunchKernelGGL((mppi_step_server_kernel<256, 2, true>), g, b, lds, st, ServerLaunch{a, z});
+    else hipLaunchKernelGGL((mppi_step_server_kernel<256, 2, false>), g, b, lds, st, ServerLaunch{a, z});
+  }
   return hipGetLastError();
 }
 

@@ -20,9 +20,11 @@ constexpr int SCORE_THREADS = 256;
 // state_fields() of mppi_capi.cpp, computed on the host.
 struct ScoreGoal {
   float gx, gy, igx, igy, pf_scale;
-  int pf_far, speed_on, pad;
+  int pf_far, speed_on;
+  float x0, y0;  // the origin: the orientation critic's robot position
+  int pad;
 };
-static_assert(sizeof(ScoreGoal) == 32, "ScoreGoal layout");
+static_assert(sizeof(ScoreGoal) == 40, "ScoreGoal layout");
 
 struct ScoreArgs {
   // paths, trajectory-major (device memory)
@@ -49,10 +51,15 @@ struct ScoreArgs {
   int pf_far, speed_on;
   float vmax, thr, pen;
   float w_path, w_slope, w_speed, w_obs;
+  // the orientation critic (mppi_critics::w_orientation; 0: the cost has no such term) and its robot
+  // position, the origin (with `log`: goals[p].x0, y0).  The slope mode is the caller's choice of
+  // lw / rw: null scores the body path.
+  float w_orient, x0, y0;
   // outputs (device memory; any may be null)
   float* cost;          // [n]
   float* terms;         // [n][4] path, slope, speed, obstacle (16-byte aligned)
   int32_t* collisions;  // [n]
+  float* orient;        // [n] the orientation critic's value (mppi_get_cost_terms5)
   // with `log` only: [n] each path's own costmap of cm's geometry (device pointers; an episode's
   // costmap slot, mppi_batch_score), or null: every path on cm
   const float* const* cm_path;

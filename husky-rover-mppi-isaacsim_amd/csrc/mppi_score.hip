@@ -204,9 +204,10 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
   float acc = 0.0f;  // this wave's chain
   int col = 0;
   float pl[3] = {0.0f, 0.0f, 0.0f}, pr[3] = {0.0f, 0.0f, 0.0f};  // slope: the previous even waypoint
+  float ex[2] = {0.0f, 0.0f}, ey[2] = {0.0f, 0.0f};  // path wave: waypoints L - 2 and L - 1 (the orientation critic)
 
   // the goal terms: kernel arguments, or (LOG) the lane's own path's, each wave loading its critic's
-  float gx = a.gx, gy = a.gy, igx = a.igx, igy = a.igy, pf_scale = a.pf_scale;
+  float gx = a.gx, gy = a.gy, igx = a.igx, igy = a.igy, pf_scale = a.pf_scale, x0 = a.x0, y0 = a.y0;
   int pf_far = a.pf_far, speed_on = a.speed_on;
   if constexpr (LOG) {
     if (p < a.n) {
@@ -218,6 +219,8 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
         igy = g->igy;
         pf_scale = g->pf_scale;
         pf_far = g->pf_far;
+        x0 = g->x0;
+        y0 = g->y0;
       } else if (role == 2) {
         speed_on = g->speed_on;
       }
@@ -242,6 +245,16 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     const int te = min(t0 + len, L);  // this lane's waypoints of the chunk: [t0, te)
     if (role == 0) {
       const float* q = sm.a[0] + lane * ROW3;
+      if (a.w_orient != 0.0f || a.orient) {  // (uniform) the path's last two waypoints, whichever chunks hold them
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int tw = L - 2 + i;
+          if (tw >= t0 && tw < te) {
+            ex[i] = q[3 * (tw - t0)];
+            ey[i] = q[3 * (tw - t0) + 1];
+          }
+        }
+      }
       if (pf_far) {  // critics_warp.py:111-119: the terminal waypoint against the intermediate goal
         const int tl = L - 1;
         if (tl >= t0 && tl < te) {
@@ -312,8 +325,19 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
   if (role == 0 && p < a.n) {
     const float pf = sm.term[0][lane], sw = sm.term[1][lane], sp = sm.term[2][lane], ob = sm.term[3][lane];
     if (a.terms) *reinterpret_cast<float4*>(a.terms + 4 * (size_t)p) = make_float4(pf, sw, sp, ob);
-    if (a.cost) {  // critics_warp.py:325-329
+    // critics_warp.py:44-82, as the rollout kernels' orientation_term; a path of one waypoint has no
+    // last displacement: 0
+    float po = 0.0f;
+    if (L >= 2) {
+      const float xd = gx - x0, yd = gy - y0;
+      const float s = (xd * (ex[1] - ex[0])) + (yd * (ey[1] - ey[0]));
+      const float den = fabsf(xd) + fabsf(yd);
+      po = (s <= 0.0f && den != 0.0f) ? (-s) / den : 0.0f;
+    }
+    if (a.orient) a.orient[p] = po;
+    if (a.cost) {  // critics_warp.py:324-329
       float cost = a.w_path * pf;
+      if (a.w_orient != 0.0f) cost = a.w_orient * po + cost;  // the menu's first line, when it exists
       cost = cost + a.w_slope * sw;
       cost = cost + a.w_speed * sp;
       cost = cost + a.w_obs * ob;

@@ -93,7 +93,14 @@ class MppiBatchIo(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("states", "mask", "reset", "seeds", "cmd", "plan")]
 
 
+class MppiCritics(C.Structure):
+    """mppi_critics: the critic set of a context or of a variant row (8 bytes)."""
+    _fields_ = [("slope_mode", C.c_int32), ("w_orientation", C.c_float)]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
+COST_TERMS5 = COST_TERMS + ("orientation",)           # mppi_get_cost_terms5
+SLOPE_MODES = {"wheels": 0, "body": 1}                # mppi_slope_mode
 
 
 # name -> (restype, argtypes); must match include/mppi.h (tests/test_lib_symbols.py checks both ways)
@@ -123,6 +130,10 @@ _PROTOS = {
     "mppi_score_paths": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _FP, _FP, _FP, _FP,
                                    C.POINTER(MppiState), C.POINTER(MppiPathScores)]),
     "mppi_get_cost_terms": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32)]),
+    "mppi_get_cost_terms5": (C.c_int, [C.c_void_p, _FP, C.POINTER(C.c_int32)]),
+    "mppi_set_critics": (C.c_int, [C.c_void_p, C.POINTER(MppiCritics)]),
+    "mppi_get_critics": (C.c_int, [C.c_void_p, C.POINTER(MppiCritics)]),
+    "mppi_batch_set_variant_critics": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiCritics)]),
     "mppi_get_score_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_set_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "mppi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
@@ -737,6 +748,28 @@ class Engine:
                 "mppi_get_cost_terms")
         return terms, col
 
+    def cost_terms5(self):
+        """mppi_get_cost_terms5: (terms [K, 5] in COST_TERMS5 order, collisions [K]) of the last step's
+        rollouts; recombined in the critic set's order they are the bits of costs() for any set."""
+        terms = np.zeros((self.K, 5), np.float32)
+        col = np.zeros(self.K, np.int32)
+        self._c(self.lib.mppi_get_cost_terms5(self.ctx, _fp(terms), col.ctypes.data_as(C.POINTER(C.c_int32))),
+                "mppi_get_cost_terms5")
+        return terms, col
+
+    def set_critics(self, slope="wheels", w_orientation=0.0):
+        """mppi_set_critics: the slope critic on the wheel contacts ("wheels", the default) or on the
+        body path ("body", the only slope information of the 2D projection), and the weight of the
+        path-orientation critic (0: off).  Applies from the next step."""
+        k = make_critics(slope, w_orientation)
+        self._c(self.lib.mppi_set_critics(self.ctx, C.byref(k)), "mppi_set_critics")
+
+    def critics(self):
+        """mppi_get_critics: dict(slope="wheels" | "body", w_orientation)."""
+        k = MppiCritics()
+        self._c(self.lib.mppi_get_critics(self.ctx, C.byref(k)), "mppi_get_critics")
+        return critics_as_dict(k)
+
     def score_ms(self):
         """HIP-event time (ms) of the last scoring kernel (score_paths / cost_terms)."""
         ms = C.c_double()
@@ -820,6 +853,26 @@ class Engine:
 def make_policy(sigma_base=0.4, sigma_div=1.0, goal_tol=0.5, check_every=0):
     """Fill mppi_loop_policy (defaults: run()'s policy; check_every 0 = the library's 16)."""
     return MppiLoopPolicy(float(sigma_base), float(sigma_div), float(goal_tol), int(check_every))
+
+
+def make_critics(slope="wheels", w_orientation=0.0):
+    """Fill mppi_critics; ValueError names the field (the checks of mppi_set_critics that need no context)."""
+    if isinstance(slope, str):
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
+        mode = SLOPE_MODES[slope]
+    else:
+        mode = int(slope)
+        if mode not in SLOPE_MODES.values():
+            raise ValueError(f"slope mode must be 0 (wheels) or 1 (body), got {mode}")
+    w = float(w_orientation)
+    if not (np.isfinite(w) and abs(w) <= float(np.finfo(np.float32).max)):
+        raise ValueError(f"w_orientation must be a finite float32, got {w_orientation!r}")
+    return MppiCritics(mode, w)
+
+
+def critics_as_dict(k: MppiCritics):
+    return dict(slope={v: n for n, v in SLOPE_MODES.items()}[int(k.slope_mode)], w_orientation=float(k.w_orientation))
 
 
 def make_variant(proj="3d", **fields):
@@ -940,9 +993,25 @@ class Batch:
     def set_variants(self, variants):
         """The batch's variant table: a list of MppiBatchVariant or dicts (make_variant's arguments);
         an empty list clears it."""
-        rows = [_as_variant(v) for v in variants]
+        from .batch import split_variant
+        split = [(v, None) if isinstance(v, MppiBatchVariant) else split_variant(v) for v in variants]
+        rows = [_as_variant(v) for v, _ in split]
         arr = (MppiBatchVariant * max(len(rows), 1))(*rows)
         _check(self.lib, self.lib.mppi_batch_set_variants(self.h, len(rows), arr), "mppi_batch_set_variants")
+        # dicts with "slope" / "w_orientation" keys fill the critic rows; a row without them runs with
+        # the engine's set as it is now
+        crit = [k for _, k in split]
+        self.set_variant_critics([self.engine.critics() if k is None else k for k in crit]
+                                 if any(k is not None for k in crit) else [])
+
+    def set_variant_critics(self, rows):
+        """mppi_batch_set_variant_critics: variant row i runs with critic set rows[i] (MppiCritics or
+        dict(slope=, w_orientation=)); variants past the list, and episodes or tasks without a variant,
+        run with the engine's set.  An empty list clears the rows."""
+        rows = [k if isinstance(k, MppiCritics) else make_critics(**dict(k)) for k in rows]
+        arr = (MppiCritics * max(len(rows), 1))(*rows)
+        _check(self.lib, self.lib.mppi_batch_set_variant_critics(self.h, len(rows), arr),
+               "mppi_batch_set_variant_critics")
 
     def variant_default(self, proj="3d", policy=None):
         """The variant that changes nothing: the engine's params with `proj` and the policy's sigma schedule."""
@@ -1198,6 +1267,10 @@ class Group:
 
     def set_nominal(self, u1, u2):
         self._each("set_nominal", u1, u2)
+
+    def set_critics(self, slope="wheels", w_orientation=0.0):
+        """The critic set of every member (Engine.set_critics)."""
+        self._each("set_critics", slope, w_orientation)
 
     def set_async_tail(self, on=True):
         """Deferred optimal rollout on every member (Engine.set_async_tail)."""

@@ -60,6 +60,29 @@ def variant_params(params, variant, policy=None, proj="3d"):
     return out, pol, pj
 
 
+CRITIC_FIELDS = ("slope", "w_orientation")     # mppi_critics (include/mppi.h), by Engine.set_critics' names
+
+
+def split_variant(variant):
+    """A variant dict that may carry the critic keys -> (the mppi_batch_variant dict, the critic set).
+
+    "slope" ("wheels" | "body") and "w_orientation" are not fields of mppi_batch_variant: they fill
+    the batch's second table (mppi_batch_set_variant_critics).  The critic set is
+    dict(slope=, w_orientation=) with "wheels" / 0.0 for a key not given, or None when the dict
+    carries neither key: that row runs with the context's set."""
+    v = dict(variant)
+    given = {k: v.pop(k) for k in CRITIC_FIELDS if k in v}
+    if not given:
+        return v, None
+    crit = dict(slope="wheels", w_orientation=0.0)
+    crit.update(given)
+    if crit["slope"] not in ("wheels", "body"):
+        raise ValueError(f"slope must be 'wheels' or 'body', got {crit['slope']!r}")
+    if not np.isfinite(F32(crit["w_orientation"])):
+        raise ValueError(f"w_orientation must be finite, got {crit['w_orientation']!r}")
+    return v, crit
+
+
 def variant_dict(proj="3d", **fields):
     """A full variant dict: the library's default parameters (_lib.make_params) and run()'s sigma
     schedule, overridden by `fields`."""

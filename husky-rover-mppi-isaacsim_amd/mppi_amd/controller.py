@@ -241,6 +241,8 @@ class MPPI_Controller:
         self.resident = None if os.environ.get("MPPI_RESIDENT") is not None or "resident" not in eng \
             else int(eng["resident"])  # (true / false, or 0 / 1 / 2: mppi_set_option "resident")
         self.resident_idle_us = eng.get("resident_idle_us")
+        # the critic set (Engine.set_critics): the slope critic's mode and the orientation weight
+        self.critics = dict(slope=eng.get("slope", "wheels"), w_orientation=float(eng.get("w_orientation", 0.0)))
         self.step_index = 0          # Philox step counter (replaces rng.integers at :517)
         self.engine = None
         self._out = None
@@ -266,6 +268,8 @@ class MPPI_Controller:
         if self.resident_idle_us is not None:
             self.engine.set_option("resident_idle_us", int(self.resident_idle_us))
         self._tail_fresh = True
+        if self.critics != dict(slope="wheels", w_orientation=0.0):
+            self.engine.set_critics(**self.critics)
         self._upload_dem(self.surface.Z)
         self._upload_costmap(self.surface.costmap)
         H, K = self.number_of_iterations, self.number_of_trajectories
@@ -424,6 +428,15 @@ class MPPI_Controller:
         if self._cost_terms is None:
             self._cost_terms = self.engine.cost_terms()
         return self._cost_terms
+
+    def set_critics(self, slope="wheels", w_orientation=0.0):
+        """The critic set of the following steps (Engine.set_critics): slope "wheels" | "body", and the
+        path-orientation critic's weight (0: off).  Kept across warp_setup()."""
+        _lib.make_critics(slope, w_orientation)     # (ValueError before anything changes)
+        self.critics = dict(slope=slope, w_orientation=float(w_orientation))
+        if self.engine is not None:
+            self.engine.set_critics(**self.critics)
+            self._cost_terms = None
 
     def score_paths(self, traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None, state=None):
         """The critics on caller-supplied paths (Engine.score_paths): logged runs

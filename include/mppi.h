@@ -311,13 +311,42 @@ int mppi_get_costs(mppi_ctx* ctx, float* costs_host, int64_t n);
 int mppi_dump_rollouts(mppi_ctx* ctx, float* traj, float* heading, float* left_wheel,
                        float* right_wheel, float* lin_vel, float* ang_vel, float* u1, float* u2);
 
+/* ---- the critic set ----
+ * The evaluation kernel (critics_warp.py:322-329) is a menu of critic lines that the thesis switched
+ * in and out.  Beside the four of mppi_params' weights two more can be chosen per context:
+ *   slope_mode     MPPI_SLOPE_WHEELS: _avoid_slope_wheels over the wheel contacts (:327, the default);
+ *                  MPPI_SLOPE_BODY: _avoid_slope over the body path (:326, :131-166): for t = 0, 2, ..
+ *                  < H - 3, (1 + 5 |dz / (sqrt(dx dx + dy dy) + 1e-6)|)^2 between waypoints t and t + 2
+ *                  of the rollout, z the bilinear height at the body position.  The 2D projection has no
+ *                  wheel contacts (they are DEFINED zero), so this is its only slope information.  The
+ *                  dumped wheel arrays of a 3D step stay the contacts in either mode.
+ *   w_orientation  weight of _path_orientation_critic (:324, :44-82); 0 (the default): no such term.
+ *                  xd = goal_x - x, yd = goal_y - y (the robot), (x2, y2) = X[H-1] - X[H-2] of the
+ *                  rollout, s = xd x2 + yd y2, po = s <= 0 ? -s / (|xd| + |yd|) : 0, DEFINED 0 where
+ *                  |xd| + |yd| == 0 (and for a scored path of one waypoint).
+ * The cost is, in float32 and this order, c = w_orientation po (only when the weight is not 0),
+ * c += w_path path, c += w_slope slope, c += w_speed speed, c += w_obstacle obstacle.  With the
+ * default set every result keeps its bits.
+ * mppi_set_critics stops the resident server like every call outside the step set; the set then
+ * applies to mppi_step, _step_injected, _step_partial (each group member is set through
+ * mppi_group_context), mppi_get_costs, mppi_get_cost_terms and the scoring calls.  MPPI_EINVAL,
+ * naming the field, for an unknown mode, a non-finite weight, or w_orientation != 0 with
+ * num_iterations < 2. */
+enum mppi_slope_mode { MPPI_SLOPE_WHEELS = 0, MPPI_SLOPE_BODY = 1 };
+typedef struct mppi_critics { int32_t slope_mode; float w_orientation; } mppi_critics;  /* 8 bytes */
+int mppi_set_critics(mppi_ctx* ctx, const mppi_critics* critics);   /* default {WHEELS, 0} */
+int mppi_get_critics(mppi_ctx* ctx, mppi_critics* out);
+
 /* ---- path scoring and per-critic terms ----
  * _evaluate_trajectories_kernel (critics_warp.py:302-329) on paths the caller supplies: the
  * offline re-scoring of logged runs (evaluate_trajectory.py, dim = 1, paths of up to 3500
  * waypoints) and the cost of the chosen plan (MPPI_isaac.py:726-752).  Besides the weighted
  * total the four critic values are returned unweighted (the thesis compared critics by
  * commenting lines :325-329 in and out), and the number of waypoints in collision. */
-enum mppi_cost_term { MPPI_TERM_PATH = 0, MPPI_TERM_SLOPE = 1, MPPI_TERM_SPEED = 2, MPPI_TERM_OBSTACLE = 3 };
+enum mppi_cost_term {
+  MPPI_TERM_PATH = 0, MPPI_TERM_SLOPE = 1, MPPI_TERM_SPEED = 2, MPPI_TERM_OBSTACLE = 3,
+  MPPI_TERM_ORIENTATION = 4 /* mppi_get_cost_terms5 only */
+};
 typedef struct mppi_path_scores { /* host pointers, any may be NULL */
   float* cost;         /* [n]   weighted total, as costs_wp                                  */
   float* terms;        /* [n*4] unweighted critic values, mppi_cost_term order               */
@@ -333,7 +362,9 @@ typedef struct mppi_path_scores { /* host pointers, any may be NULL */
  * other fields are not read), NULL = the context's current state.  Weights, horizon (it does not
  * depend on stride), thresholds and v_max_linear are the context's params, the costmap the
  * context's.  Needs a costmap (MPPI_ESTATE otherwise), no DEM.  n * stride < 2^31.  Synchronous;
- * changes no state of the context. */
+ * changes no state of the context.  The context's critic set applies: in MPPI_SLOPE_BODY the slope
+ * critic reads traj even when wheel arrays are given, and with w_orientation != 0 `cost` has the
+ * orientation term in front (robot = origin's x, y); `terms` stays [n*4]. */
 int mppi_score_paths(mppi_ctx* ctx, int64_t n, int32_t stride, const int32_t* lengths,
                      const float* traj, const float* left_wheel, const float* right_wheel,
                      const float* lin_vel, const mppi_state* origin, mppi_path_scores* out);
@@ -341,8 +372,13 @@ int mppi_score_paths(mppi_ctx* ctx, int64_t n, int32_t stride, const int32_t* le
  * (either may be NULL): re-runs the step like mppi_dump_rollouts with the dump buffers kept on
  * the device, scores them there and copies out 20 bytes per trajectory.  terms recombined as
  * critics_warp.py:325-329 (w_path * path, += w_slope * slope, += w_speed * speed,
- * += w_obstacle * obstacle) are the bits of mppi_get_costs. */
+ * += w_obstacle * obstacle) are the bits of mppi_get_costs whenever the critic set's w_orientation
+ * is 0.  Term 1 is the slope value of the mode in force. */
 int mppi_get_cost_terms(mppi_ctx* ctx, float* terms, int32_t* collisions);
+/* The same with the orientation critic's value as a fifth term, [K*5] in mppi_cost_term order:
+ * recombined in the order of the critic set's section (the orientation line first, only when its
+ * weight is not 0) they are the bits of mppi_get_costs for any set. */
+int mppi_get_cost_terms5(mppi_ctx* ctx, float* terms5, int32_t* collisions);
 /* HIP-event time of the last scoring kernel of the context, in milliseconds. */
 int mppi_get_score_ms(mppi_ctx* ctx, double* ms);
 
@@ -425,6 +461,14 @@ int  mppi_batch_set_variants(mppi_batch* b, int32_t n, const mppi_batch_variant*
  * params overridden by the variant, with the variant's projection, advanced by the rule above with
  * the variant's sigma schedule.  Per step the rollout is launched once per projection in use. */
 int  mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant);
+/* The critic sets of the variant rows: 0 <= n <= 1024 rows, copied to device memory; n = 0 clears
+ * them.  Variant row i runs with critic row i if i < n; every other variant, and every episode or
+ * task without a variant, runs with the context's set (mppi_set_critics).  Every step of such an
+ * episode, task or device step is bitwise the mppi_step of a context with the variant's params
+ * after mppi_set_critics(row).  MPPI_EINVAL names the row and the field (the checks of
+ * mppi_set_critics).  The log scorers (mppi_batch_score, _score_tasks) use the context's set: a log
+ * has no wheel arrays, so their slope critic is the body form in either mode. */
+int  mppi_batch_set_variant_critics(mppi_batch* b, int32_t n, const mppi_critics* rows);
 
 /* ---- per-episode scene and trajectory count ----
  * The campaign's other two axes: "various terrain constraints, various number of trajectories"

@@ -18,7 +18,7 @@ sys.path[:0] = [HERE, ROOT]
 import bench  # noqa: E402
 from loopcount import kernel_lines  # noqa: E402
 
-KERNEL = "roles_kernelILi256ELi3ELi0ELb0E"
+KERNEL = "roles_kernelILi256ELi3ELi0ELb0ELb0E"
 
 
 def main():

@@ -12,6 +12,10 @@
 // ended claim the next task of a list in device memory (campaign_claim / campaign_refill); the one
 // word two workgroups of a launch share is the list's counter, taken with an agent-scope atomic add.
 //
+// A scored task list (mppi_batch_set_tasks_scored): the finish kernel's scored form is the campaign form
+// whose advance lane also extends the log scorer's critic chains (mppi_score_chain.h) by the row it
+// logs, in a per-lane record, and writes the task's score row with its result; the log is optional.
+//
 // The device-resident step (mppi_batch_step_device): mppi_batch_ingest_kernel writes states held in
 // device memory into the records ahead of the noise launch, and the finish kernel's step form hands
 // the command and the plan out instead of advancing.  The noise and rollout kernels are the same.
@@ -142,7 +146,12 @@ __device__ __forceinline__ void episode_goal_fields(BatchEpisode* ep, float x, f
 // variant index and scene record, which the next step's kernels read.  With the list exhausted the
 // lane goes inactive and leaves the pinned count.  Returns whether a task was loaded (the caller
 // then zeroes the lane's nominal double buffer).
-__device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep) {
+// SCORED (a scored list): the lane's accumulator record starts over with the claimed task: every
+// chain, pending term and count zero, and the goal terms of the task's start, which are the critics'
+// scalar parts the lane's record has just received.
+template <bool SCORED = false>
+__device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep,
+                                               BatchScoreAcc* acc = nullptr) {
   for (;;) {
     const int i = __hip_atomic_fetch_add(q.next_task, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (i >= q.n) {
@@ -183,6 +192,17 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
     ep->s1 = t->s1;
     ep->s2 = t->s2;
     episode_goal_fields(ep, x, y, gx, gy, b.horizon);
+    if constexpr (SCORED) {
+      BatchScoreAcc z{};
+      z.x0 = x;
+      z.y0 = y;
+      z.igx = ep->igx;
+      z.igy = ep->igy;
+      z.pf_scale = ep->pf_scale;
+      z.pf_far = ep->pf_far;
+      z.speed_on = ep->speed_on;
+      *acc = z;
+    }
     ep->active = 1;
     ep->cur = 0;
     ep->seed = t->seed;
@@ -202,9 +222,11 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
 // through LDS, and on a new task every thread zeroes its share of both halves of the lane's nominal
 // double buffer (what mppi_batch_set_episode does with a memset).  Every thread of the workgroup
 // calls this: the branch is uniform, the barrier is not inside it.
+template <bool SCORED = false>
 __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep,
-                                                bool ended, int tid, int nthreads, int* got) {
-  if (tid == 0) *got = (ended && campaign_claim(b, q, e, ep)) ? 1 : 0;
+                                                bool ended, int tid, int nthreads, int* got,
+                                                BatchScoreAcc* acc = nullptr) {
+  if (tid == 0) *got = (ended && campaign_claim<SCORED>(b, q, e, ep, acc)) ? 1 : 0;
   __syncthreads();
   if (*got) {
     float* u = b.unom + (size_t)e * 4 * b.H;
@@ -231,20 +253,38 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // workgroup copies the 4H + 12 outputs to io.plan[e]: no advance rule, no goal test, no log row, no
 // touch of the active count.  The state stays what the ingest kernel (below) wrote.  The io pointers
 // are this form's own third kernel argument, as the queue is the campaign form's.
+//
+// SCORED (a list set by mppi_batch_set_tasks_scored): the campaign form whose advance lane also
+// extends the four critic chains of the log scorer by the row in hand (mppi_score_chain.h: the same
+// device functions, the same order in t) and the float64 path length, in the lane's BatchScoreAcc,
+// and writes the task's BatchTaskScore with its result.  Two terms wait for the next row, because the
+// scorer admits them only when that row exists: the near path term of row t (the sum runs over
+// t < L - 1) and the slope term of even row s (it needs row s + 1).  The record is loaded at the head,
+// beside lane_steps; only this lane reads or writes it.  With q.log null (keep_log = 0) no row is
+// written: a uniform branch around the eight stores.  The queue, the yardstick and the two tables
+// are this form's third kernel argument (BatchScoredCampaign).
 __device__ __forceinline__ const BatchCampaign* queue_of() { return nullptr; }
 __device__ __forceinline__ const BatchCampaign* queue_of(const BatchCampaign& q) { return &q; }
 __device__ __forceinline__ const BatchCampaign* queue_of(const BatchIo&) { return nullptr; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchScoredCampaign& s) { return &s.q; }
 __device__ __forceinline__ const BatchIo* io_of() { return nullptr; }
 __device__ __forceinline__ const BatchIo* io_of(const BatchCampaign&) { return nullptr; }
 __device__ __forceinline__ const BatchIo* io_of(const BatchIo& io) { return &io; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchScoredCampaign&) { return nullptr; }
+template <class... Q>
+__device__ __forceinline__ const BatchScoredCampaign* scored_of(const Q&...) { return nullptr; }
+__device__ __forceinline__ const BatchScoredCampaign* scored_of(const BatchScoredCampaign& s) { return &s; }
 template <class... Queue>
 __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
                                                                          const Queue... queue) {
   static_assert(sizeof...(Queue) <= 1, "at most the one queue, or the one io block");
-  constexpr bool CAMPAIGN = (std::is_same<Queue, BatchCampaign>::value || ...);
+  constexpr bool SCORED = (std::is_same<Queue, BatchScoredCampaign>::value || ...);
+  constexpr bool CAMPAIGN = (std::is_same<Queue, BatchCampaign>::value || ...) || SCORED;
   constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...);
-  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP ? 1 : 0), "the third argument is a BatchCampaign or a BatchIo");
+  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP ? 1 : 0),
+                "the third argument is a BatchCampaign, a BatchScoredCampaign or a BatchIo");
   const BatchCampaign* q = queue_of(queue...);
+  const BatchScoredCampaign* sc = scored_of(queue...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
@@ -255,6 +295,12 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   if constexpr (CAMPAIGN) {
     ln = q->lane[e];
     lane_steps = q->lane_steps[e];
+  }
+  BatchScoreAcc sa{};         // SCORED: the lane's chains so far, loaded here as lane_steps is
+  const float* cm = nullptr;  // SCORED: the task's costmap
+  if constexpr (SCORED) {
+    sa = sc->acc[e];
+    cm = sc->cm;
   }
   FinishArgs f = f_in;
   const int H = f.H, E = 2 * H + 2;
@@ -277,6 +323,9 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     if (s.dem >= 0) {  // row 0 of the optimal rollout reads the DEM
       f.Z = b.scene->dem_z[s.dem];
       f.ntab = b.scene->dem_ntab[s.dem];
+    }
+    if constexpr (SCORED) {
+      if (s.cm >= 0) cm = b.scene->cms[s.cm];
     }
   }
   const int cur_buf = ep->cur;
@@ -369,7 +418,9 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     const double d0 = (double)ld(4 * H + 3), d1 = (double)ld(4 * H + 4), d2 = (double)ld(4 * H + 5);
     const double nn = __builtin_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
     const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
-    if (row < (CAMPAIGN ? ln.max_steps : b.log_cap)) {
+    bool log_row = row < (CAMPAIGN ? ln.max_steps : b.log_cap);
+    if constexpr (SCORED) log_row = log_row && q->log != nullptr;
+    if (log_row) {
       float* lg = CAMPAIGN ? q->log + ((size_t)ln.log_base + row) * 8 : b.log + ((size_t)e * b.log_cap + row) * 8;
       lg[0] = x;
       lg[1] = y;
@@ -396,6 +447,36 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     ep->step = ep->step + 1;
     ep->steps_run = row + 1;
     const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
+    if constexpr (SCORED) {
+      // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
+      if (!sa.pf_far) {  // the near branch: the term of row - 1 enters now that this row exists
+        if (row >= 1) sa.path = sa.path + sa.path_pend;
+        sa.path_pend = chain::path_near(x, y, gx, gy);
+      }
+      if ((row & 1) == 0) {  // an even row s: its term (rows s - 2 and s) waits for row s + 1
+        const float c3[3] = {x, y, z};
+        if (row >= 2) sa.slope_pend = chain::slope_one(sa.pe, c3);
+        sa.pe[0] = x;
+        sa.pe[1] = y;
+        sa.pe[2] = z;
+      } else if (row >= 3) {
+        sa.slope = sa.slope + sa.slope_pend;
+      }
+      if (sa.speed_on) sa.speed = chain::speed(sa.speed, sc->vmax, v);
+      const float c = cm[chain::cm_index(sc->hw, sc->res_c, sc->cm_size, x, y)];
+      const chain::ObstacleAcc oa = chain::obstacle(sa.obs, sa.col, c, sc->thr, sc->pen);
+      sa.obs = oa.acc;
+      sa.col = oa.col;
+      if (row % 5 == 0) {  // compute_length: the sampled rows 0, 5, 10, ..., float64, no contraction
+        if (row > 0) {
+          const double dx = (double)x - (double)sa.sx, dy = (double)y - (double)sa.sy, dz = (double)z - (double)sa.sz;
+          sa.length = sa.length + __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+        }
+        sa.sx = x;
+        sa.sy = y;
+        sa.sz = z;
+      }
+    }
     if constexpr (CAMPAIGN) {
       q->lane_steps[e] = lane_steps + 1;
       ended = reached || row + 1 >= ln.max_steps;
@@ -416,13 +497,36 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
         r->reached = reached ? 1 : 0;
         r->flags = 3;
       }
+      if constexpr (SCORED) {
+        if (ended) {  // L = row + 1 rows: the far branch and the orientation critic read the last ones
+          const float pf = sa.pf_far ? chain::path_far(x, y, sa.igx, sa.igy, sa.pf_scale) : sa.path;
+          const float po = row >= 1 ? chain::orientation(gx, gy, sa.x0, sa.y0, sa.lx, sa.ly, x, y) : 0.0f;
+          BatchTaskScore* o = sc->score + ln.task;
+          o->cost = chain::combine(sc->w_path, sc->w_slope, sc->w_speed, sc->w_obs, sc->w_orient, pf, sa.slope,
+                                   sa.speed, sa.obs, po);
+          o->terms[0] = pf;
+          o->terms[1] = sa.slope;
+          o->terms[2] = sa.speed;
+          o->terms[3] = sa.obs;
+          o->collisions = sa.col;
+          o->rows = row + 1;
+          o->length = sa.length;
+        } else {  // (the claim resets the record of a lane whose task ended)
+          sa.lx = x;
+          sa.ly = y;
+          sc->acc[e] = sa;
+        }
+      }
     } else if (reached) {
       ep->active = 0;
       ep->reached = 1;
       __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-  if constexpr (CAMPAIGN) campaign_refill(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw));
+  if constexpr (SCORED)
+    campaign_refill<true>(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw), sc->acc + e);
+  else if constexpr (CAMPAIGN)
+    campaign_refill(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw));
 }
 
 // The first fill of a campaign: every lane claims as a finishing lane does.  Grid E, one wave each.
@@ -430,6 +534,13 @@ __global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b,
   __shared__ int got;
   const int e = blockIdx.x;
   campaign_refill(b, q, e, b.ep + e, true, (int)threadIdx.x, 64, &got);
+}
+
+// The first fill of a scored list: the claim that also resets the lane's accumulator record.
+__global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b, const BatchScoredCampaign s) {
+  __shared__ int got;
+  const int e = blockIdx.x;
+  campaign_refill<true>(b, s.q, e, b.ep + e, true, (int)threadIdx.x, 64, &got, s.acc + e);
 }
 
 // The way into the episode record for a plant that lives on the device (mppi_batch_step_device):
@@ -517,12 +628,26 @@ hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, con
 }
 
 hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_claim_kernel, dim3((unsigned)b.E), dim3(64), 0, st, b, q);
+  void (*k)(const BatchArgs, const BatchCampaign) = mppi_batch_claim_kernel;  // (the scored list's claim is an overload)
+  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, q);
   return hipGetLastError();
 }
 
 hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
                                         hipStream_t st) {
   hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, q);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_claim_scored(const BatchArgs& b, const BatchScoredCampaign& s, hipStream_t st) {
+  void (*k)(const BatchArgs, const BatchScoredCampaign) = mppi_batch_claim_kernel;
+  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_scored(const FinishArgs& f, const BatchArgs& b, const BatchScoredCampaign& s,
+                                      size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchScoredCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f,
+                     b, s);
   return hipGetLastError();
 }

@@ -29,7 +29,7 @@ enum TaskError {
   kTaskSlotGeometry,  // a live slot set under another geometry than the context's current one
   kTaskKRange,        // K outside [1, context K] (0: the context's)
   kTaskMaxSteps,      // max_steps < 1
-  kTaskRows,          // the caps sum to more rows than the arena may have
+  kTaskRows,          // the caps sum to more rows than the arena may have (a list that keeps a log)
 };
 
 class BatchTaskBook {
@@ -43,6 +43,7 @@ class BatchTaskBook {
     base_.clear();
     total_ = 0;
     max_cap_ = 0;
+    keep_log_ = true;
   }
 
   // May `t` be listed?  The rules of the per-episode setters (BatchSceneBook::set_episode_scene /
@@ -64,32 +65,38 @@ class BatchTaskBook {
   }
 
   // Replace the list.  On an error nothing changes; `bad` receives the first offending task.
+  // keep_log false (a scored list that keeps no log, mppi_batch_set_tasks_scored): there is no arena, so
+  // no task has base rows and the caps' sum has no limit; every other rule stands.
   TaskError set(const std::vector<TaskSpec>& tasks, int variant_rows, const BatchSceneBook& book,
                 const SceneGeom& dem_now, const SceneGeom& cm_now, int64_t context_K, int* bad = nullptr,
-                SceneKind* kind = nullptr) {
-    std::vector<int64_t> base(tasks.size());
+                SceneKind* kind = nullptr, bool keep_log = true) {
+    std::vector<int64_t> base(keep_log ? tasks.size() : 0);
     int64_t rows = 0;
     int cap = 0;
     for (size_t i = 0; i < tasks.size(); ++i) {
       if (bad) *bad = (int)i;
       const TaskError err = check(tasks[i], variant_rows, book, dem_now, cm_now, context_K, kind);
       if (err != kTaskOk) return err;
+      if (tasks[i].max_steps > cap) cap = tasks[i].max_steps;
+      if (!keep_log) continue;
       base[i] = rows;
       rows += tasks[i].max_steps;
       if (rows > kMaxRows) return kTaskRows;
-      if (tasks[i].max_steps > cap) cap = tasks[i].max_steps;
     }
     t_ = tasks;
     base_.swap(base);
     total_ = rows;
     max_cap_ = cap;
     K_ = context_K;
+    keep_log_ = keep_log;
     return kTaskOk;
   }
 
   const TaskSpec& task(int i) const { return t_[(size_t)i]; }
   // Task i's rows of the arena are [base(i), base(i) + max_steps): the prefix sum of the caps before it.
-  int64_t base(int i) const { return base_[(size_t)i]; }
+  // A list that keeps no log hands out no base rows: -1, and no rows in all.
+  int64_t base(int i) const { return keep_log_ ? base_[(size_t)i] : -1; }
+  bool keeps_log() const { return keep_log_; }
   int64_t total_rows() const { return total_; }
   int max_cap() const { return max_cap_; }
 
@@ -155,6 +162,7 @@ class BatchTaskBook {
   std::vector<int64_t> base_;
   int64_t total_ = 0, K_ = 0;
   int max_cap_ = 0;
+  bool keep_log_ = true;
 };
 
 // The batch steps the claim rule needs for tasks of the given lengths on `lanes` lanes: greedy list

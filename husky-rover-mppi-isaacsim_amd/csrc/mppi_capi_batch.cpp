@@ -69,6 +69,13 @@ struct mppi_batch {
   DeviceBuf<float> tlog;             // the log arena, [sum of max_steps][8]
   std::vector<int> lane_steps;       // [E] as last read
   enum Campaign { kNotStarted, kUnfinished, kComplete } campaign = kNotStarted;
+  // a scored list (mppi_batch_set_tasks_scored): the yardstick as taken when the list was set (the
+  // pointers and the costmap geometry are filled in by each run), the lanes' accumulator records and
+  // the tasks' score rows
+  bool scored = false;
+  BatchScoredCampaign yard{};
+  DeviceBuf<BatchScoreAcc> d_acc;     // [E]
+  DeviceBuf<BatchTaskScore> d_score;  // [N]
 };
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
 static_assert(sizeof(mppi_critics) == sizeof(BatchCriticRow), "mppi_critics layout");
@@ -406,6 +413,7 @@ void task_list_clear(mppi_batch* b) {
   b->tasks.clear();
   b->res.clear();
   b->campaign = mppi_batch::kNotStarted;
+  b->scored = false;
 }
 
 BatchCampaign campaign_args(mppi_batch* b) {
@@ -415,7 +423,7 @@ BatchCampaign campaign_args(mppi_batch* b) {
   q.lane = b->d_lane;
   q.next_task = b->d_count;
   q.lane_steps = b->d_count + 1;
-  q.log = b->tlog;
+  q.log = b->tbook.keeps_log() ? b->tlog.get() : nullptr;
   q.ep_var = b->d_ep_var;
   q.rec = b->d_tab->rec;
   q.n = b->tbook.size();
@@ -473,6 +481,15 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
   b->tbook.projections(vproj, proj, use_proj);
   const BatchCampaign q = campaign_args(b);
   const size_t E = (size_t)b->E;
+  // a scored list: the yardstick of the list, the queue, the tables and the costmap of this run
+  BatchScoredCampaign sq = b->yard;
+  sq.q = q;
+  sq.acc = b->d_acc;
+  sq.score = b->d_score;
+  sq.cm = c->cmap.cm;
+  sq.cm_size = c->cmap.size;
+  sq.hw = c->cmap.hw;
+  sq.res_c = c->cmap.res;
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
   if (b->campaign == mppi_batch::kNotStarted) {
     // the first fill: every lane empty and counted active, then one claim each
@@ -483,7 +500,13 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
     __atomic_store_n(b->active_count.get(), b->E, __ATOMIC_RELEASE);
     b->lane_steps.assign(E, 0);
     b->campaign = mppi_batch::kUnfinished;
-    HIP_TRY(launch_batch_claim(z, q, c->stream));
+    if (b->scored) {  // no task has a score yet; the claim resets the lanes' records
+      HIP_TRY(hipMemsetAsync(b->d_score, 0, (size_t)N * sizeof(BatchTaskScore), c->stream));
+      HIP_TRY(hipMemsetAsync(b->d_acc, 0, E * sizeof(BatchScoreAcc), c->stream));
+      HIP_TRY(launch_batch_claim_scored(z, sq, c->stream));
+    } else {
+      HIP_TRY(launch_batch_claim(z, q, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   const int before = *std::max_element(b->lane_steps.begin(), b->lane_steps.end());
@@ -494,7 +517,10 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
       HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
       for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
         if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-      HIP_TRY(launch_batch_finish_campaign(f, z, q, pl.fin_lds_bytes, c->stream));
+      if (b->scored)
+        HIP_TRY(launch_batch_finish_scored(f, z, sq, pl.fin_lds_bytes, c->stream));
+      else
+        HIP_TRY(launch_batch_finish_campaign(f, z, q, pl.fin_lds_bytes, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     done += m;
@@ -1062,7 +1088,11 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
                     b->log_cap, yardstick, out, rows, "batch_score");
 }
 
-int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks) {
+// mppi_batch_set_tasks and mppi_batch_set_tasks_scored: one list, one set of checks.  scored: the
+// lanes score as they run, with `yardstick` (NULL: the context's params); keep_log false (scored
+// lists only): no arena.
+static int set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks, bool scored,
+                     const mppi_batch_variant* yardstick, bool keep_log) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
   if (n < 0) return fail(MPPI_EINVAL, "tasks: n must be >= 0");
   if (n > 0 && !tasks) return fail(MPPI_EINVAL, "null argument");
@@ -1082,7 +1112,7 @@ int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks)
   int bad = -1;
   SceneKind kind = kSceneDem;
   const TaskError err = fresh.set(specs, (int)b->variants.size(), b->book, dem_geom(c), costmap_geom(c),
-                                  c->p.num_trajectories, &bad, &kind);
+                                  c->p.num_trajectories, &bad, &kind, keep_log);
   if (err != kTaskOk) return fail(MPPI_EINVAL, task_error(b, bad, tasks[bad], err, kind));
   // the list is replaced from here on: an unfinished campaign of the old one is abandoned
   if (b->campaign == mppi_batch::kUnfinished)
@@ -1092,9 +1122,13 @@ int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks)
   const size_t N = (size_t)n, E = (size_t)b->E;
   // the arena, and max_cap rows behind it: the scorer stages every path of a tile up to the tile's
   // longest, so it reads (and drops) up to that many rows past a short last task
-  const size_t log_bytes = ((size_t)fresh.total_rows() + (size_t)fresh.max_cap()) * 8 * sizeof(float);
+  // (a list that keeps no log has no arena, and gives an earlier list's back: no kernel is in flight)
+  const size_t log_bytes = keep_log ? ((size_t)fresh.total_rows() + (size_t)fresh.max_cap()) * 8 * sizeof(float) : 0;
+  if (!keep_log) b->tlog.reset();
   if (b->d_tasks.grow(N * sizeof(BatchTask)) || b->d_res.grow(N * sizeof(BatchTaskResult)) ||
-      b->d_lane.grow(E * sizeof(BatchLane)) || b->d_count.grow((E + 1) * sizeof(int)) || b->tlog.grow(log_bytes)) {
+      b->d_lane.grow(E * sizeof(BatchLane)) || b->d_count.grow((E + 1) * sizeof(int)) ||
+      (keep_log && b->tlog.grow(log_bytes)) ||
+      (scored && (b->d_acc.grow(E * sizeof(BatchScoreAcc)) || b->d_score.grow(N * sizeof(BatchTaskScore))))) {
     (void)hipGetLastError();
     return fail(MPPI_EHIP, "tasks: allocation of the tables of " + std::to_string(n) + " tasks and a log arena of " +
                                std::to_string(log_bytes) + " bytes failed");
@@ -1125,10 +1159,62 @@ int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks)
   }
   HIP_TRY(hipMemcpyAsync(b->d_tasks, dev.data(), N * sizeof(BatchTask), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->d_res, 0, N * sizeof(BatchTaskResult), c->stream));
+  if (scored) HIP_TRY(hipMemsetAsync(b->d_score, 0, N * sizeof(BatchTaskScore), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // dev is pageable and dies here
   b->tbook = fresh;
   b->tasks.assign(tasks, tasks + n);
   b->res.assign(N, BatchTaskResult{});
+  b->scored = scored;
+  if (scored) {  // the yardstick is taken here (as score_logs takes it when it scores a log)
+    const mppi_params& p = c->p;
+    BatchScoredCampaign& y = b->yard;
+    y = BatchScoredCampaign{};
+    y.vmax = p.v_max_linear;
+    y.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+    y.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+    y.w_path = yardstick ? yardstick->w_path : p.w_path;
+    y.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+    y.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+    y.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+    y.w_orient = c->crit.w_orientation;
+  }
+  return MPPI_OK;
+}
+
+int mppi_batch_set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks) {
+  return set_tasks(b, n, tasks, false, nullptr, true);
+}
+
+int mppi_batch_set_tasks_scored(mppi_batch* b, int32_t n, const mppi_batch_task* tasks,
+                                const mppi_batch_variant* yardstick, int32_t keep_log) {
+  return set_tasks(b, n, tasks, true, yardstick, keep_log != 0);
+}
+
+int mppi_batch_get_task_scores(mppi_batch* b, int32_t first, int32_t count, mppi_path_scores* out, int32_t* rows,
+                               double* length) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (b->tbook.empty() || !b->scored)
+    return fail(MPPI_ESTATE, "batch_get_task_scores: the task list was not set scored: call mppi_batch_set_tasks_scored");
+  if (first < 0 || count < 0 || (int64_t)first + count > b->tbook.size())
+    return fail(MPPI_EINVAL, "batch_get_task_scores: tasks [" + std::to_string(first) + ", " +
+                                 std::to_string((int64_t)first + count) + ") outside the list of " +
+                                 std::to_string(b->tbook.size()) + " tasks");
+  if (count == 0) return MPPI_OK;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<BatchTaskScore> sc((size_t)count);
+  HIP_TRY(hipMemcpyAsync(sc.data(), b->d_score + first, (size_t)count * sizeof(BatchTaskScore), hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int32_t i = 0; i < count; ++i) {
+    const BatchTaskScore& r = sc[(size_t)i];
+    if (out && out->cost) out->cost[i] = r.cost;
+    if (out && out->terms) std::memcpy(out->terms + 4 * (size_t)i, r.terms, sizeof(r.terms));
+    if (out && out->collisions) out->collisions[i] = r.collisions;
+    if (rows) rows[i] = r.rows;
+    if (length) length[i] = r.length;
+  }
   return MPPI_OK;
 }
 
@@ -1201,6 +1287,7 @@ int mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t cou
   if ((int64_t)first + count > b->res[i].steps)
     return fail(MPPI_EINVAL, "task " + std::to_string(i) + ": log range beyond the " + std::to_string(b->res[i].steps) +
                                  " steps the task has taken");
+  if (!b->tbook.keeps_log()) return fail(MPPI_ESTATE, "batch_get_task_log: the task list keeps no log (keep_log = 0)");
   if (count == 0) return MPPI_OK;
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
@@ -1219,6 +1306,7 @@ int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, c
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (b->tbook.empty()) return fail(MPPI_ESTATE, "batch_score_tasks: no task list: call mppi_batch_set_tasks first");
+  if (!b->tbook.keeps_log()) return fail(MPPI_ESTATE, "batch_score_tasks: the task list keeps no log (keep_log = 0)");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score_tasks: no costmap: call mppi_set_costmap first");
   const int s = b->tbook.mismatch(kSceneCostmap, b->book, costmap_geom(c));
   if (s >= 0)

@@ -329,6 +329,49 @@ struct BatchCampaign {
 hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st);
 hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
                                         hipStream_t st);
+// ---- a scored task list (mppi_batch_set_tasks_scored / _get_task_scores) ----
+// The advance lane of the finish kernel extends the four critic chains of the log scorer
+// (mppi_score_chain.h) by the row it logs, and writes the task's score row with its result: what
+// mppi_batch_score_tasks(b, yardstick, NULL, ...) computes from the log, bit for bit, without a log.
+// One record per lane: read and written by the advance lane of workgroup e only, reset by the claim,
+// which also fills the goal terms of the task's start (the scorer's ScoreGoal).
+struct BatchScoreAcc {
+  float path, slope, speed, obs;  // the four chains
+  float path_pend;                // the near branch's term of the last row: it enters when the next row arrives
+  float slope_pend;               // the slope term of the last even row: it enters when the odd row behind it arrives
+  int col;                        // collisions
+  float pe[3];                    // the previous even waypoint
+  float lx, ly;                   // the last row's x, y (the orientation critic reads the last two rows)
+  float sx, sy, sz;               // the last sampled waypoint (rows 0, 5, 10, ...) of `length`
+  float x0, y0, igx, igy, pf_scale;  // the goal terms of the task's start (state_fields())
+  int pf_far, speed_on;
+  double length;                  // compute_length of evaluate_trajectory.py:43-53 so far, float64
+};
+static_assert(sizeof(BatchScoreAcc) == 96, "BatchScoreAcc layout");
+struct BatchTaskScore {  // one row per task, zero until the task ends (and for a task that took no step)
+  float cost;
+  float terms[4];  // path, slope (body form), speed, obstacle
+  int collisions;
+  int rows;        // = the task's steps
+  int pad;
+  double length;
+};
+static_assert(sizeof(BatchTaskScore) == 40, "BatchTaskScore layout");
+// The scored forms' own third kernel argument (BatchArgs does not grow): the queue, then the
+// yardstick as taken when the list was set, the costmap geometry of the run and the two tables.
+struct BatchScoredCampaign {
+  BatchCampaign q;          // q.log null: the list keeps no log and no row is written
+  BatchScoreAcc* acc;       // [E]
+  BatchTaskScore* score;    // [n]
+  const float* cm;          // the context's costmap: a task without a costmap slot
+  int cm_size;
+  float hw, res_c;
+  float vmax, thr, pen;
+  float w_path, w_slope, w_speed, w_obs, w_orient;
+};
+hipError_t launch_batch_claim_scored(const BatchArgs& b, const BatchScoredCampaign& s, hipStream_t st);
+hipError_t launch_batch_finish_scored(const FinishArgs& f, const BatchArgs& b, const BatchScoredCampaign& s,
+                                      size_t lds, hipStream_t st);
 // ---- the device-resident step of a batch (mppi_batch_step_device) ----
 // One step of every set episode for a plant that is not the controller's own model: the ingest
 // kernel writes the caller's states into the episode records, the noise and rollout kernels run as

@@ -31,6 +31,7 @@
 // staged, into the same LDS rows (strides 37 and 13), so the score phase is the same code; pf_far
 // and speed_on become per-lane branches.
 #include "mppi_score.h"
+#include "mppi_score_chain.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -156,26 +157,9 @@ __device__ __forceinline__ void stage_chunk(const ScoreArgs& a, Stage<VEC>& r, S
   stage_array<VEC, 1, stage_floats(1, VEC), STORE>(a.v, r.v, sm.v, ROWV, p0, a.n, a.stride, t0, len, tid);
 }
 
-// critics_warp.py:190-218: (1 + 5 |dz / (d + 1e-6)|)^2 between waypoints t and t + 2 of one wheel.
-__device__ __forceinline__ float slope_one(const float (&p)[3], const float (&c)[3]) {
-  const float dz = c[2] - p[2];
-  const float dx = c[0] - p[0], dy = c[1] - p[1];
-  const float d = sqrtf(dx * dx + dy * dy);
-  const float ratio = fabsf(dz / (d + 1e-6f));
-  const float s = 1.0f + 5.0f * ratio;
-  return s * s;
-}
-
-// critics_warp.py:244-248 (oracle costmap_at): clamp(trunc(clamp(f, -1, size)), 0, size - 1) is
-// trunc(clamp(f, 0, size - 1)); a NaN coordinate indexes cell 0, as the oracle's fmax / fmin.
-__device__ __forceinline__ int cm_index(const ScoreArgs& a, float x, float y) {
-  const float fx = (x + a.hw) / a.res_c;
-  const float fy = ((-y) + a.hw) / a.res_c;
-  const float top = (float)(a.cm_size - 1);
-  const int ix = (int)fminf(fmaxf(fx, 0.0f), top);
-  const int iy = (int)fminf(fmaxf(fy, 0.0f), top);
-  return ix + a.cm_size * iy;
-}
+// The chains' steps are mppi_score_chain.h's: one statement of each rule, shared with the advance lane
+// of the scored campaign (mppi_batch_kernels.h).
+using chain::slope_one;
 
 // LOG: the paths are a batch's log with per-path goal terms (see above); VEC = 1, WHEELS = false there.
 // RAGGED (mppi_batch_score_tasks): the LOG loader with a base row per path (ScoreArgs::base_row).
@@ -257,15 +241,10 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
       }
       if (pf_far) {  // critics_warp.py:111-119: the terminal waypoint against the intermediate goal
         const int tl = L - 1;
-        if (tl >= t0 && tl < te) {
-          const float dx = q[3 * (tl - t0)] - igx;
-          const float dy = q[3 * (tl - t0) + 1] - igy;
-          acc = (dx * dx + dy * dy) * pf_scale;
-        }
+        if (tl >= t0 && tl < te) acc = chain::path_far(q[3 * (tl - t0)], q[3 * (tl - t0) + 1], igx, igy, pf_scale);
       } else {  // :120-123
         const int tp = min(te, L - 1);
-        for (int t = t0; t < tp; ++t)
-          acc = acc + 10.0f * (fabsf(q[3 * (t - t0)] - gx) + fabsf(q[3 * (t - t0) + 1] - gy));
+        for (int t = t0; t < tp; ++t) acc = acc + chain::path_near(q[3 * (t - t0)], q[3 * (t - t0) + 1], gx, gy);
       }
     } else if (role == 1) {
       const float* ql = sm.a[WHEELS ? 1 : 0] + lane * ROW3;
@@ -296,20 +275,15 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     } else if (role == 2) {
       if (speed_on) {  // critics_warp.py:281-300
         const float* q = sm.v + lane * ROWV;
-        for (int t = t0; t < te; ++t) {
-          const float vt = q[t - t0];
-          acc = acc + (a.vmax - vt) / (vt + 0.0001f);
-        }
+        for (int t = t0; t < te; ++t) acc = chain::speed(acc, a.vmax, q[t - t0]);
       }
     } else {
       const float* q = sm.a[0] + lane * ROW3;
       for (int t = t0; t < te; ++t) {  // critics_warp.py:244-262
-        const float c = cm[cm_index(a, q[3 * (t - t0)], q[3 * (t - t0) + 1])];
-        if (c > a.thr) {
-          acc = acc + a.pen;
-          ++col;
-        }
-        acc = acc + c;
+        const float c = cm[chain::cm_index(a.hw, a.res_c, a.cm_size, q[3 * (t - t0)], q[3 * (t - t0) + 1])];
+        const chain::ObstacleAcc oa = chain::obstacle(acc, col, c, a.thr, a.pen);
+        acc = oa.acc;
+        col = oa.col;
       }
     }
     __syncthreads();  // every wave is done with the staged chunk
@@ -328,19 +302,10 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     // critics_warp.py:44-82, as the rollout kernels' orientation_term; a path of one waypoint has no
     // last displacement: 0
     float po = 0.0f;
-    if (L >= 2) {
-      const float xd = gx - x0, yd = gy - y0;
-      const float s = (xd * (ex[1] - ex[0])) + (yd * (ey[1] - ey[0]));
-      const float den = fabsf(xd) + fabsf(yd);
-      po = (s <= 0.0f && den != 0.0f) ? (-s) / den : 0.0f;
-    }
+    if (L >= 2) po = chain::orientation(gx, gy, x0, y0, ex[0], ey[0], ex[1], ey[1]);
     if (a.orient) a.orient[p] = po;
     if (a.cost) {  // critics_warp.py:324-329
-      float cost = a.w_path * pf;
-      if (a.w_orient != 0.0f) cost = a.w_orient * po + cost;  // the menu's first line, when it exists
-      cost = cost + a.w_slope * sw;
-      cost = cost + a.w_speed * sp;
-      cost = cost + a.w_obs * ob;
+      float cost = chain::combine(a.w_path, a.w_slope, a.w_speed, a.w_obs, a.w_orient, pf, sw, sp, ob, po);
       if constexpr (LOG)
         if (L == 0) cost = 0.0f;  // an episode with no rows: cost 0 whatever the weights
       a.cost[p] = cost;

@@ -206,6 +206,10 @@ _PROTOS = {
     "mppi_batch_get_task_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "mppi_batch_score_tasks": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
                                          C.POINTER(MppiPathScores), C.POINTER(C.c_int32)]),
+    "mppi_batch_set_tasks_scored": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchTask),
+                                              C.POINTER(MppiBatchVariant), C.c_int32]),
+    "mppi_batch_get_task_scores": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MppiPathScores),
+                                             C.POINTER(C.c_int32), _DP]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
                                          C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_int32)]),
 }
@@ -1124,13 +1128,47 @@ class Batch:
         return rows
 
     # ---- the task queue: N tasks on the E episodes as lanes (mppi_batch_set_tasks / _run_tasks) ----
-    def set_tasks(self, tasks):
+    def set_tasks(self, tasks, scored=None, keep_log=True):
         """The batch's task list: MppiBatchTask (make_task) or dicts of make_task's arguments; an empty
-        list clears it.  The results are reset."""
+        list clears it.  The results are reset.
+
+        scored: None (a plain list), or the yardstick every task is scored with as it runs
+        (mppi_batch_set_tasks_scored): True for the engine's params, or a MppiBatchVariant / dict whose
+        weights, collision_threshold and collision_penalty are used; task_scores() then reads the
+        scores.  keep_log=False (scored lists only): no log arena is allocated, so task_log and
+        score_tasks raise and the sum of the step caps has no limit."""
         rows = [t if isinstance(t, MppiBatchTask) else make_task(**dict(t)) for t in tasks]
         arr = (MppiBatchTask * max(len(rows), 1))(*rows)
-        _check(self.lib, self.lib.mppi_batch_set_tasks(self.h, len(rows), arr), "mppi_batch_set_tasks")
+        if scored is None or scored is False:
+            if not keep_log:
+                raise ValueError("keep_log=False needs a scored list (scored=True or a yardstick): "
+                                 "without a log nothing of a plain list's runs could be scored")
+            _check(self.lib, self.lib.mppi_batch_set_tasks(self.h, len(rows), arr), "mppi_batch_set_tasks")
+        else:
+            y = None if scored is True else C.byref(_as_variant(scored))
+            _check(self.lib, self.lib.mppi_batch_set_tasks_scored(self.h, len(rows), arr, y, 1 if keep_log else 0),
+                   "mppi_batch_set_tasks_scored")
         self.n_tasks = len(rows)
+
+    def task_scores(self, first=0, count=None):
+        """mppi_batch_get_task_scores: the scores the lanes computed as they ran tasks
+        [first, first + count) of a scored list (count None: to the end of the list).  Returns
+        dict(cost [n], terms [n, 4] in COST_TERMS order, collisions [n], rows [n], length [n] float64);
+        a task that has not ended, or took no step, has zeros."""
+        N = int(getattr(self, "n_tasks", 0))
+        first = int(first)
+        n = N - first if count is None else int(count)
+        if first < 0 or n < 0 or first + n > N:
+            raise ValueError(f"tasks [{first}, {first + n}) outside the list of {N} tasks")
+        out = dict(cost=np.zeros(n, np.float32), terms=np.zeros((n, 4), np.float32),
+                   collisions=np.zeros(n, np.int32), rows=np.zeros(n, np.int32), length=np.zeros(n, np.float64))
+        i32 = C.POINTER(C.c_int32)
+        sc = MppiPathScores(_fp(out["cost"]), _fp(out["terms"]), out["collisions"].ctypes.data_as(i32))
+        _check(self.lib, self.lib.mppi_batch_get_task_scores(self.h, first, n, C.byref(sc),
+                                                             out["rows"].ctypes.data_as(i32),
+                                                             out["length"].ctypes.data_as(_DP)),
+               "mppi_batch_get_task_scores")
+        return out
 
     def run_tasks(self, n_steps, proj="3d", policy=None):
         """Advance the campaign by up to n_steps batch steps (it stops when every task has ended; a

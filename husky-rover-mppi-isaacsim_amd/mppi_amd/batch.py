@@ -199,6 +199,65 @@ def campaign_makespan(lengths, lanes):
     return steps
 
 
+LENGTH_STRIDE = 5    # compute_length samples every fifth waypoint (evaluate_trajectory.py:43-53)
+
+
+def path_length(rows):
+    """compute_length of evaluate_trajectory.py:43-53 on logged waypoints, in float64: the `length` of
+    a scored task list (mppi_batch_get_task_scores).  rows: [L, >= 3] float32, x, y, z first (a task
+    log).  Over the sampled rows 0, 5, 10, ... < L: for consecutive sampled rows a -> b, each
+    difference of the float32 coordinates widened first, d = sqrt((dx dx + dy dy) + dz dz), summed in
+    row order.  Fewer than two sampled rows give 0."""
+    rows = np.asarray(rows, dtype=F32)
+    p = rows.reshape(len(rows), rows.shape[-1] if rows.ndim > 1 else 3)[::LENGTH_STRIDE, :3].astype(np.float64)
+    length = np.float64(0.0)
+    for a, b in zip(p[:-1], p[1:]):
+        dx, dy, dz = b[0] - a[0], b[1] - a[1], b[2] - a[2]
+        length = length + np.sqrt((dx * dx + dy * dy) + dz * dz)
+    return length
+
+
+SUMMARY_FIELDS = ("cost", "path", "slope", "speed", "obstacle", "length")
+
+
+def campaign_summary(results, by=None):
+    """The table of a campaign, per group of tasks: what the thesis's stats_results.py prints per
+    controller variant.  Plain numpy, no GPU.
+
+    results: one dict per task with `reached`, `cost`, `terms` (4 values: path, slope, speed,
+    obstacle), `collisions` and `length`: MPPI_Controller.run_campaign(..., score=...) returns them
+    (its per-task dicts and the score arrays; see `campaign_results`).  by: one group key per task
+    (task_variant, say); None: one group, keyed None.
+
+    Returns {key: dict(count, reached, collided (runs with at least one collision), mean=dict(cost,
+    path, slope, speed, obstacle, length), std=the same fields)} in float64, the standard deviation
+    the population's (numpy's default), keys in order of first appearance."""
+    results = list(results)
+    keys = [None] * len(results) if by is None else list(by)
+    if len(keys) != len(results):
+        raise ValueError(f"{len(results)} results but {len(keys)} group keys")
+    groups = {}
+    for k, r in zip(keys, results):
+        groups.setdefault(k, []).append(r)
+    out = {}
+    for k, rs in groups.items():
+        terms = np.asarray([np.asarray(r["terms"], np.float64).reshape(4) for r in rs])
+        cols = dict(cost=np.asarray([r["cost"] for r in rs], np.float64), path=terms[:, 0], slope=terms[:, 1],
+                    speed=terms[:, 2], obstacle=terms[:, 3], length=np.asarray([r["length"] for r in rs], np.float64))
+        out[k] = dict(count=len(rs), reached=sum(1 for r in rs if r["reached"]),
+                      collided=sum(1 for r in rs if int(r["collisions"]) > 0),
+                      mean={f: float(np.mean(cols[f])) for f in SUMMARY_FIELDS},
+                      std={f: float(np.std(cols[f])) for f in SUMMARY_FIELDS})
+    return out
+
+
+def campaign_results(tasks, scores):
+    """run_campaign's (per-task dicts, score arrays) as the per-task dicts campaign_summary takes:
+    each task's dict with its cost, terms, collisions and length added."""
+    return [dict(t, cost=scores["cost"][i], terms=scores["terms"][i], collisions=scores["collisions"][i],
+                 length=scores["length"][i]) for i, t in enumerate(tasks)]
+
+
 def normalise_heading(hv):
     """Row 0 of heading_sim widened to float64 and divided by sqrt((h0 h0 + h1 h1) + h2 h2) (the sum
     left to right, every operation rounded once), each component rounded to float32."""

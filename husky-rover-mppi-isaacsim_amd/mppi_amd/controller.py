@@ -637,7 +637,7 @@ class MPPI_Controller:
 
     def run_campaign(self, starts, headings, goals, seeds=None, lanes=64, max_loops=None, proj="3d", policy=None,
                      variants=None, task_variant=None, score=None, dems=None, costmaps=None, task_dem=None,
-                     task_costmap=None, task_trajectories=None):
+                     task_costmap=None, task_trajectories=None, log=True):
         """run_batch for N tasks on `lanes` episodes (mppi_batch_set_tasks / _run_tasks):
         the lane whose task ends (goal reached, or its step cap) takes the next task of the list on the
         GPU in the same step, so a campaign of runs of very different lengths keeps every lane busy
@@ -649,8 +649,18 @@ class MPPI_Controller:
         one per task.  task_variant / task_dem / task_costmap / task_trajectories: run_batch's
         episode_* arguments, per task.  lanes: the episodes the campaign runs on (at most the tasks).
 
-        Returns what run_batch returns, one dict per task (with `score` the pair).
+        With `score` the lanes score their tasks as they run (mppi_batch_set_tasks_scored): the scores
+        are those of the log scorer, bit for bit, with each task's `length` (mppi_amd.batch.path_length
+        of its log) beside them.  log=False (needs `score`): no log arena is allocated, so a campaign's
+        size is not bounded by the sum of its step caps; the per-task dicts then hold `loops`,
+        `reached` and the final `x`, `y` only.
+
+        Returns what run_batch returns, one dict per task (with `score` the pair; mppi_amd.batch
+        campaign_results / campaign_summary turn the pair into the per-variant table).
         """
+        scored = not (score is None or score is False)
+        if not log and not scored:
+            raise ValueError("log=False needs score=True or a yardstick: without a log nothing else is kept of a run")
         starts = np.asarray(starts, np.float64).reshape(-1, 2)
         N = starts.shape[0]
         headings = np.asarray(headings, np.float64).reshape(N, 3)
@@ -677,20 +687,25 @@ class MPPI_Controller:
             batch.set_tasks([_lib.make_task(_lib.make_state(starts[i, 0], starts[i, 1], headings[i], 0.0, 0.0,
                                                             goals[i, 0], goals[i, 1], self.std_dev_u1,
                                                             self.std_dev_u2),
-                                            seeds[i], caps[i], tv[i], td[i], tc[i], tk[i]) for i in range(N)])
+                                            seeds[i], caps[i], tv[i], td[i], tc[i], tk[i]) for i in range(N)],
+                            scored=score if scored else None, keep_log=bool(log))
             done = 0
             while done < N:     # every task ends within its cap, so the campaign ends
                 done, _ = batch.run_tasks(max(caps), proj, pol)
             out = []
             for i in range(N):
                 info = batch.task(i)
+                if not log:
+                    out.append(dict(x=info["state"].x, y=info["state"].y, loops=info["steps"],
+                                    reached=info["reached"]))
+                    continue
                 rows = batch.task_log(i, 0, info["steps"])
                 out.append(dict(x=[starts[i, 0]] + list(rows[:, 0]), y=[starts[i, 1]] + list(rows[:, 1]),
                                 z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
                                 loops=info["steps"], reached=info["reached"]))
-            if score is None or score is False:
+            if not scored:
                 return out
-            return out, batch.score_tasks(None if score is True else score)
+            return out, batch.task_scores()
         finally:
             batch.close()
 

@@ -577,6 +577,39 @@ int  mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t co
 int  mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
                             mppi_path_scores* out, int32_t* rows);
 
+/* ---- a scored task list: every task's score as it runs, with or without a log ----
+ * Almost every campaign ends in mppi_batch_score_tasks with one yardstick, which needs the log arena
+ * (32 bytes per step of every cap) and a second pass over it.  A list set scored is scored by the
+ * lane that runs it: in the step that logs a row, the same lane extends the scorer's four critic
+ * chains by that row, and when the task ends its score row is written beside its result.
+ * Contract, per ended task i: cost, terms[4] (path, slope in the body form, speed, obstacle),
+ * collisions and rows are bit for bit what mppi_batch_score_tasks(b, yardstick, NULL, ...) returns
+ * for a logged run of the same list: origin = the task's start and goal, the task's own costmap
+ * (its slot's, or the context's), the yardstick's weights, collision_threshold and
+ * collision_penalty (its other fields are not read; NULL = the context's params), and the context's
+ * w_orientation in front of the cost; the yardstick, w_orientation and v_max_linear are taken when
+ * the list is set.  `length` is compute_length of evaluate_trajectory.py:43-53 on the task's
+ * waypoints in float64: over the sampled rows 0, 5, 10, ... < rows, the sum in row order of
+ * sqrt((dx dx + dy dy) + dz dz) between consecutive sampled rows, each difference of the float32
+ * coordinates widened first; fewer than two sampled rows give 0.  A task that took no step, has
+ * not ended or was not yet claimed has a row of zeros, as mppi_batch_score_tasks scores a path
+ * without rows.
+ * mppi_batch_set_tasks_scored is mppi_batch_set_tasks (the same checks and refusals, the same rules
+ * about replacing or clearing a list; mppi_batch_run_tasks and mppi_batch_get_task as before) with
+ * the yardstick and keep_log.  keep_log != 0: everything mppi_batch_set_tasks gives, and the scores.
+ * keep_log = 0: no arena is allocated and no row is written, so the caps' sum has no limit and the
+ * device holds 184 bytes per task (the task, its result, its score row) whatever the caps;
+ * mppi_batch_get_task_log and mppi_batch_score_tasks then answer MPPI_ESTATE (the list keeps no
+ * log). */
+int  mppi_batch_set_tasks_scored(mppi_batch* b, int32_t n, const mppi_batch_task* tasks,
+                                 const mppi_batch_variant* yardstick, int32_t keep_log);
+/* The score rows of tasks [first, first + count): out's arrays of count (out, or any of its arrays,
+ * may be NULL), rows [count] and length [count] (may be NULL).  One copy of count rows of 40 bytes,
+ * no kernel launch.  MPPI_ESTATE when the standing list was not set scored; MPPI_EINVAL for a range
+ * outside the list. */
+int  mppi_batch_get_task_scores(mppi_batch* b, int32_t first, int32_t count, mppi_path_scores* out, int32_t* rows,
+                                double* length);
+
 /* ---- a batch's device-resident step: the plant is the caller's ----
  * mppi_batch_run feeds row 0 of the optimal rollout back as the next state: the plant is the
  * controller's own model.  The Isaac loop (visual_terrain_stack_full_terrain.py:466-515) hands

@@ -1639,7 +1639,8 @@ int mppi_debug_hold(int32_t device, void* stream, int32_t groups, int32_t lds_by
 int mppi_selftest(mppi_ctx* c, int32_t what, int64_t n, uint64_t seed, int64_t* mismatches) {
   if (!c || !mismatches) return fail(MPPI_EINVAL, "null argument");
   if (int rc_q = quiesce(c)) return rc_q;
-  if (what < 0 || what > 5 || n < 0 || (what == 5 && n > 2 + 0x4C000000LL)) return fail(MPPI_EINVAL, "bad selftest arguments");
+  if (what < 0 || what > 6 || n < 0 || (what == 5 && n > 2 + 0x4C000000LL) || (what == 6 && n > (8193LL << 18)))
+    return fail(MPPI_EINVAL, "bad selftest arguments");
   HIP_TRY(hipSetDevice(c->device));
   DeviceBuf<unsigned long long> d;
   HIP_TRY(d.alloc(sizeof(unsigned long long)));

@@ -23,6 +23,41 @@ namespace mppi {
 MPPI_HD float bits_f(uint32_t u) { return __builtin_bit_cast(float, u); }
 MPPI_HD uint32_t f_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 
+// ------------------------------------------------------------------ near-unit norms
+// Square root and reciprocal of the squared norm n of a vector that is unit up to rounding, both
+// correctly rounded, for |bits(n) - bits(1)| <= kNear1 (the rollout chain's re-normalisations).
+//  b = RN(sqrt(n)) = bits (bits(n) + bits(1)) >> 1 (see lean_norm_near1 in mppi_kernels.hip), so
+//    |bits(b) - bits(1)| <= 1024.
+//  y = RN(1 / b): with b = 1 + k 2^-23 (k >= 0) 1 / b = 1 - k 2^-23 + k^2 2^-46 - ..., with
+//    b = 1 - j 2^-24 it is 1 + j 2^-24 + j^2 2^-48 + ...; d = 1 - b is exact (Sterbenz) and
+//    y = fma(d, 1 + 2^-13, 1) rounds 1 + d + d 2^-13 once.  Below 1 the extra term d 2^-13 = j 2^-37
+//    breaks the tie of an odd j upwards (as j^2 2^-48 does) and is far under half an ulp (2^-24),
+//    so an even j stays; above 1 it is k 2^-36 <= 2^-26, under half an ulp (2^-25) of [0.5, 1),
+//    as k^2 2^-46 is.  No transcendental, no Newton step.
+//    Written as ONE fma on b: with c = 1 + 2^-13 the real number 1 + d c is (1 + c) - b c, both
+//    constants are floats (1 + c = 2 + 2^-13) and an fma rounds the exact value once, so
+//    fma(b, -c, 1 + c) gives the bits of fma(1 - b, c, 1) without the subtraction (on the device
+//    v_fmamk_f32 with 1 + c in a VGPR: one instruction per site where v_rcp_f32 + 2 fma stood).
+// tests/native/near1_recip_check.cpp checks y against 1.0f / b and the chain's quotients against
+// a / b for every divisor of the range and every significand of a.
+constexpr int kNear1 = 2047;
+struct Recip {
+  float b, y;  // the divisor and its refined reciprocal
+};
+MPPI_HD Recip recip_near1(float n) {
+  Recip r;
+  r.b = bits_f((f_bits(n) + 0x3F800000u) >> 1);
+  r.y = __builtin_fmaf(r.b, -1.0001220703125f, 2.0001220703125f);  // 1 + (1 - b) (1 + 2^-13)
+  return r;
+}
+// a / r.b from the refined reciprocal: q0 = a y, the residual formed negated, E = b q0 - a, and ONE
+// correction q = q0 - E y (the chain's quotient sequence, lean_div_s; each lane of lean_div2 / lean_div3)
+MPPI_HD float recip_div(float a, const Recip& r) {
+  const float q0 = a * r.y;
+  const float e0 = __builtin_fmaf(r.b, q0, -a);
+  return __builtin_fmaf(-e0, r.y, q0);
+}
+
 // ------------------------------------------------------------------ log
 // Cephes logf; x must be a positive normal float (Box-Muller: x in [2^-24, 1]).
 MPPI_HD float dm_logf(float x) {

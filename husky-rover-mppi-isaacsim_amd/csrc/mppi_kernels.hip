@@ -59,9 +59,7 @@ constexpr bool kFastMath = false;
 // dependency chain, and its range guards are off the critical path.
 constexpr bool kChainFast = true;
 
-struct Recip {
-  float b, y;
-};
+// (Recip, the divisor b and its refined reciprocal y: mppi_detmath.h)
 __device__ __forceinline__ bool div_ok(float v) {
   const float a = fabsf(v);
   return a >= 9.094947017729282e-13f && a <= 1.099511627776e12f;  // 2^-40 .. 2^40
@@ -328,7 +326,7 @@ __device__ __forceinline__ void lean_init(Lean& l) {
   l.nlo = kLeanNhi;
   l.nhi = kLeanNlo;
 }
-constexpr int kNear1 = 4095;  // sqrt_near1: squared norms within 4095 ulps of 1
+// (kNear1 = 2047, mppi_detmath.h: recip_near1 takes squared norms within 2047 ulps of 1)
 constexpr int kLeanEmin40 = -39;  // |a| >= 2^-40 <=> frexp exponent >= -39
 __device__ __forceinline__ bool lean_bad(const Lean& l) {
   return (l.emin < kLeanEmin) | (l.nlo < kLeanNlo) | (l.nhi > kLeanNhi) | (l.n1lo < 0x3F800000 - kNear1) |
@@ -401,26 +399,18 @@ __device__ __forceinline__ float sqrt_cr2(float n) {
 // k^2 2^-51 - ...: for |k| < 5792 the quadratic term never crosses a rounding boundary (even k:
 // it stays within half an ulp of the grid point, odd k: it moves the midpoint down), so
 // RN(sqrt(n)) = 1 + floor(k / 2) ulp above 1, 1 - ceil(k / 2) ulp below: in bits,
-// C + ((bits(n) - C) >> 1) = (bits(n) + C) >> 1 with C = bits(1.0f).  Guarded to |k| <= 4095.
+// C + ((bits(n) - C) >> 1) = (bits(n) + C) >> 1 with C = bits(1.0f).  The reciprocal of that root,
+// within 1024 ulps of 1 for |k| <= 2047 (kNear1, the guard), is one fma with no
+// transcendental (recip_near1, mppi_detmath.h: correctly rounded there, so the quotients of
+// lean_div_s / lean_div2 / lean_div3 are the IEEE ones as with the refined v_rcp_f32).
 __device__ __forceinline__ Recip lean_norm_near1(float n, Lean& l) {
   const int nb = __builtin_bit_cast(int, n);
   l.n1lo = min(l.n1lo, nb);
   l.n1hi = max(l.n1hi, nb);
-  Recip r;
-  r.b = __builtin_bit_cast(float, (int)((unsigned)(nb + 0x3F800000) >> 1));
-  const float y0 = __builtin_amdgcn_rcpf(r.b);
-  r.y = __builtin_fmaf(__builtin_fmaf(-r.b, y0, 1.0f), y0, y0);
-  return r;
+  return recip_near1(n);
 }
-// lean_norm_near1 for a squared norm PROVEN within 4095 ulps of 1 (no guard; see orient_step)
-__device__ __forceinline__ Recip norm_near1_trusted(float n) {
-  const int nb = __builtin_bit_cast(int, n);
-  Recip r;
-  r.b = __builtin_bit_cast(float, (int)((unsigned)(nb + 0x3F800000) >> 1));
-  const float y0 = __builtin_amdgcn_rcpf(r.b);
-  r.y = __builtin_fmaf(__builtin_fmaf(-r.b, y0, 1.0f), y0, y0);
-  return r;
-}
+// lean_norm_near1 for a squared norm PROVEN within 2047 ulps of 1 (no guard; see orient_step)
+__device__ __forceinline__ Recip norm_near1_trusted(float n) { return recip_near1(n); }
 __device__ __forceinline__ Recip lean_norm2(float n, Lean& l) {
   const int nb = __builtin_bit_cast(int, n);
   l.nlo = min(l.nlo, nb);
@@ -437,9 +427,7 @@ __device__ __forceinline__ Recip lean_norm2(float n, Lean& l) {
 // keep the sign of a (lean_div needed a copysign there).
 __device__ __forceinline__ float lean_div_s(float a, const Recip& r, Lean& l) {
   l.emin = min(l.emin, __builtin_amdgcn_frexp_expf(a));
-  const float q0 = a * r.y;
-  const float e0 = __builtin_fmaf(r.b, q0, -a);
-  return __builtin_fmaf(-e0, r.y, q0);
+  return recip_div(a, r);
 }
 // (a.x, a.y) / r.b, each lane lean_div_s (G = 0: numerators proven in range, no guard)
 template <int G = 1>
@@ -486,7 +474,7 @@ struct Head {  // heading vector (x, y packed)
 // from the previous one, the surface normal n and sin / cos / (1 - cos) of w dt.
 // Guards of the fast path (F): only the two vectors that can come out arbitrary are checked,
 //   p = h - (h.n) n: every component 0 or |.| >= 2^-40, |p|^2 in [2^-80, 2^80];
-//   r (the Rodrigues rotation): every component 0 or |.| >= 2^-40, |r|^2 within 4095 ulps of 1.
+//   r (the Rodrigues rotation): every component 0 or |.| >= 2^-40, |r|^2 within 2047 ulps of 1.
 // The rest follows.  t = p / |p| has components 0 or >= 2^-40 / 2^40 = 2^-80 (the quotient guard),
 // and with p's quotients exact |t|^2 = 1 + e, |e| <= ~14 ulps (3-term sum of squares of correctly
 // rounded quotients by a correctly rounded square root of a 3-term sum: ~5u + 2u + 3u + 2u), so
@@ -3485,6 +3473,40 @@ __global__ __launch_bounds__(256) void mppi_selftest_kernel(int what, int64_t n,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
       const float x = i < 2 ? (i == 0 ? -0.0f : 0.0f) : bits_f(0x33800000u + (uint32_t)(i - 2));
       if (f_bits(sqrt_bm(x)) != f_bits(sqrtf(x))) ++local;
+    }
+    if (local) atomicAdd(bad_count, local);
+    return;
+  }
+  if (what == 6) {  // the near-unit normalisation (lean_norm_near1 + lean_div3) against sqrtf(n) and a / sqrtf(n):
+    // squared norm n = the float (i >> 18) - 4096 ulps from 1 (n = 8193 * 2^18 items cover +-4096 ulps), three
+    // numerators per item from a hash of i (any sign and significand, exponents in [-30, 30]; items 0 and 1 of
+    // every norm are +0 and -0).  A norm beyond kNear1 ulps MUST come back flagged, one within must not.
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const int k = (int)(i >> 18) - 4096;
+      const float nn = bits_f((uint32_t)(0x3F800000 + k));
+      auto mk = [](uint32_t h) {
+        h ^= h >> 15;
+        h *= 0x2C1B3C6Du;
+        h ^= h >> 12;
+        return bits_f((h & 0x807FFFFFu) | ((127u - 30u + ((h >> 23) & 0xFFu) % 61u) << 23));
+      };
+      const uint32_t h = (uint32_t)i * 0x9E3779B1u + (uint32_t)(i >> 32) + (uint32_t)seed * 0x85EBCA6Bu;
+      float a0 = mk(h), a1 = mk(h + 0x68E31DA4u), a2 = mk(h + 0xB5297A4Du);
+      if ((i & 0x3FFFF) == 0) a0 = a1 = a2 = 0.0f;
+      if ((i & 0x3FFFF) == 1) a0 = a1 = a2 = -0.0f;
+      Lean l;
+      lean_init(l);
+      const Recip rr = lean_norm_near1(nn, l);
+      f2 q01;
+      float q2;
+      lean_div3<1>(f2{a0, a1}, a2, rr, l, q01, q2);
+      const bool flagged = lean_bad(l);
+      const bool inside = k >= -kNear1 && k <= kNear1;
+      const float sr = sqrtf(nn);
+      if (flagged == inside) ++local;
+      else if (inside && (f_bits(rr.b) != f_bits(sr) || f_bits(q01.x) != f_bits(a0 / sr) ||
+                          f_bits(q01.y) != f_bits(a1 / sr) || f_bits(q2) != f_bits(a2 / sr)))
+        ++local;
     }
     if (local) atomicAdd(bad_count, local);
     return;

@@ -798,7 +798,13 @@ int mppi_rollout_python25d(mppi_ctx* ctx, int64_t n, int32_t H, const double* x0
  * chain's quotient (refined reciprocal, one residual correction) against a/b
  * for every significand of a and n / 2^23 divisor significands ((seed + 8191 k)
  * mod 2^23); what = 5 the noise radius' square root (sqrt_bm) against sqrtf
- * for -0, +0 and the n - 2 floats from 2^-24 up (n <= 2 + 0x4C000000); *mismatches receives the count of in-range results that differ in
+ * for -0, +0 and the n - 2 floats from 2^-24 up (n <= 2 + 0x4C000000); what = 6
+ * the chain's normalisation of a vector that is already unit (square root and
+ * reciprocal without a transcendental, three quotients) against sqrtf and a/b for
+ * the squared norms (i >> 18) - 4096 ulps from 1, i < n <= 8193 * 2^18, with 2^18
+ * numerator triples each (zeros and both signs among them): a norm beyond 2047
+ * ulps must come back flagged for the IEEE redo and counts as a mismatch if it
+ * does not; *mismatches receives the count of in-range results that differ in
  * any bit (0 expected). */
 int mppi_selftest(mppi_ctx* ctx, int32_t what, int64_t n, uint64_t seed, int64_t* mismatches);
 

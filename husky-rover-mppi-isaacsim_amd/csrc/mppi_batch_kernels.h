@@ -19,6 +19,11 @@
 // The device-resident step (mppi_batch_step_device): mppi_batch_ingest_kernel writes states held in
 // device memory into the records ahead of the noise launch, and the finish kernel's step form hands
 // the command and the plan out instead of advancing.  The noise and rollout kernels are the same.
+//
+// Tracked device steps (mppi_batch_step_tracked): the ingest kernel's tracked form gives the device
+// step the notion of a run: it logs the row an ingested state makes, extends the scorer's chains by it
+// (the scored form's own device functions), tests the goal and the step cap and writes the run's
+// result; the finish kernel's tracked step form keeps the command for the next row.
 #pragma once
 
 // The normals of every active episode's current step, [blocks][2][H][256] per episode, addressed as
@@ -263,6 +268,65 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // beside lane_steps; only this lane reads or writes it.  With q.log null (keep_log = 0) no row is
 // written: a uniform branch around the eight stores.  The queue, the yardstick and the two tables
 // are this form's third kernel argument (BatchScoredCampaign).
+//
+// TRACKED (mppi_batch_step_tracked): the step form with one more store pair: (v, w) into the
+// episode's tracking record, where the next tracked ingest finds the command its row is paired with.
+// The io block and the records are this form's third kernel argument (BatchTrackedIo).
+
+// Row `row` of a path enters the accumulator: (x, y, z) and v, what the log row holds; (gx, gy) the
+// path's goal, cm its costmap.  The one statement of the rule for the scored campaign's advance lane
+// and the tracked ingest.  Y: the block that carries the yardstick (BatchScoredCampaign, BatchTrack).
+template <class Y>
+__device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
+                                                 float y, float z, float v, float gx, float gy) {
+  if (!sa.pf_far) {  // the near branch: the term of row - 1 enters now that this row exists
+    if (row >= 1) sa.path = sa.path + sa.path_pend;
+    sa.path_pend = chain::path_near(x, y, gx, gy);
+  }
+  if ((row & 1) == 0) {  // an even row s: its term (rows s - 2 and s) waits for row s + 1
+    const float c3[3] = {x, y, z};
+    if (row >= 2) sa.slope_pend = chain::slope_one(sa.pe, c3);
+    sa.pe[0] = x;
+    sa.pe[1] = y;
+    sa.pe[2] = z;
+  } else if (row >= 3) {
+    sa.slope = sa.slope + sa.slope_pend;
+  }
+  if (sa.speed_on) sa.speed = chain::speed(sa.speed, yd.vmax, v);
+  const float c = cm[chain::cm_index(yd.hw, yd.res_c, yd.cm_size, x, y)];
+  const chain::ObstacleAcc oa = chain::obstacle(sa.obs, sa.col, c, yd.thr, yd.pen);
+  sa.obs = oa.acc;
+  sa.col = oa.col;
+  if (row % 5 == 0) {  // compute_length: the sampled rows 0, 5, 10, ..., float64, no contraction
+    if (row > 0) {
+      const double dx = (double)x - (double)sa.sx, dy = (double)y - (double)sa.sy, dz = (double)z - (double)sa.sz;
+      sa.length = sa.length + __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+    }
+    sa.sx = x;
+    sa.sy = y;
+    sa.sz = z;
+  }
+}
+
+// The score row of a path that ended with row `row` at (x, y), into table[index]: L = row + 1 rows; the
+// far branch and the orientation critic read the last ones (sa.lx, sa.ly: row - 1).
+template <class Y, class Index>
+__device__ __forceinline__ void score_write(BatchTaskScore* table, Index index, const BatchScoreAcc& sa, const Y& yd,
+                                            int row, float x, float y, float gx, float gy) {
+  const float pf = sa.pf_far ? chain::path_far(x, y, sa.igx, sa.igy, sa.pf_scale) : sa.path;
+  const float po = row >= 1 ? chain::orientation(gx, gy, sa.x0, sa.y0, sa.lx, sa.ly, x, y) : 0.0f;
+  BatchTaskScore* o = table + index;
+  o->cost = chain::combine(yd.w_path, yd.w_slope, yd.w_speed, yd.w_obs, yd.w_orient, pf, sa.slope, sa.speed, sa.obs,
+                           po);
+  o->terms[0] = pf;
+  o->terms[1] = sa.slope;
+  o->terms[2] = sa.speed;
+  o->terms[3] = sa.obs;
+  o->collisions = sa.col;
+  o->rows = row + 1;
+  o->length = sa.length;
+}
+
 __device__ __forceinline__ const BatchCampaign* queue_of() { return nullptr; }
 __device__ __forceinline__ const BatchCampaign* queue_of(const BatchCampaign& q) { return &q; }
 __device__ __forceinline__ const BatchCampaign* queue_of(const BatchIo&) { return nullptr; }
@@ -274,15 +338,21 @@ __device__ __forceinline__ const BatchIo* io_of(const BatchScoredCampaign&) { re
 template <class... Q>
 __device__ __forceinline__ const BatchScoredCampaign* scored_of(const Q&...) { return nullptr; }
 __device__ __forceinline__ const BatchScoredCampaign* scored_of(const BatchScoredCampaign& s) { return &s; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchTrackedIo&) { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchTrackedIo& t) { return &t.io; }
+template <class... Q>
+__device__ __forceinline__ BatchTrackRec* track_of(const Q&...) { return nullptr; }
+__device__ __forceinline__ BatchTrackRec* track_of(const BatchTrackedIo& t) { return t.rec; }
 template <class... Queue>
 __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
                                                                          const Queue... queue) {
   static_assert(sizeof...(Queue) <= 1, "at most the one queue, or the one io block");
   constexpr bool SCORED = (std::is_same<Queue, BatchScoredCampaign>::value || ...);
   constexpr bool CAMPAIGN = (std::is_same<Queue, BatchCampaign>::value || ...) || SCORED;
-  constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...);
+  constexpr bool TRACKED = (std::is_same<Queue, BatchTrackedIo>::value || ...);
+  constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...) || TRACKED;
   static_assert(sizeof...(Queue) == (CAMPAIGN || STEP ? 1 : 0),
-                "the third argument is a BatchCampaign, a BatchScoredCampaign or a BatchIo");
+                "the third argument is a BatchCampaign, a BatchScoredCampaign, a BatchIo or a BatchTrackedIo");
   const BatchCampaign* q = queue_of(queue...);
   const BatchScoredCampaign* sc = scored_of(queue...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -396,6 +466,11 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
         io->cmd[2 * (size_t)e] = ld(2 * H);
         io->cmd[2 * (size_t)e + 1] = ld(3 * H);
       }
+      if constexpr (TRACKED) {  // the command the episode's next row is paired with
+        BatchTrackRec* tr = track_of(queue...) + e;
+        tr->v = ld(2 * H);
+        tr->w = ld(3 * H);
+      }
       ep->cur = cur_buf ^ 1;
       ep->step = ep->step + 1;
     }
@@ -447,36 +522,8 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     ep->step = ep->step + 1;
     ep->steps_run = row + 1;
     const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
-    if constexpr (SCORED) {
-      // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
-      if (!sa.pf_far) {  // the near branch: the term of row - 1 enters now that this row exists
-        if (row >= 1) sa.path = sa.path + sa.path_pend;
-        sa.path_pend = chain::path_near(x, y, gx, gy);
-      }
-      if ((row & 1) == 0) {  // an even row s: its term (rows s - 2 and s) waits for row s + 1
-        const float c3[3] = {x, y, z};
-        if (row >= 2) sa.slope_pend = chain::slope_one(sa.pe, c3);
-        sa.pe[0] = x;
-        sa.pe[1] = y;
-        sa.pe[2] = z;
-      } else if (row >= 3) {
-        sa.slope = sa.slope + sa.slope_pend;
-      }
-      if (sa.speed_on) sa.speed = chain::speed(sa.speed, sc->vmax, v);
-      const float c = cm[chain::cm_index(sc->hw, sc->res_c, sc->cm_size, x, y)];
-      const chain::ObstacleAcc oa = chain::obstacle(sa.obs, sa.col, c, sc->thr, sc->pen);
-      sa.obs = oa.acc;
-      sa.col = oa.col;
-      if (row % 5 == 0) {  // compute_length: the sampled rows 0, 5, 10, ..., float64, no contraction
-        if (row > 0) {
-          const double dx = (double)x - (double)sa.sx, dy = (double)y - (double)sa.sy, dz = (double)z - (double)sa.sz;
-          sa.length = sa.length + __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
-        }
-        sa.sx = x;
-        sa.sy = y;
-        sa.sz = z;
-      }
-    }
+    // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
+    if constexpr (SCORED) score_extend_row(sa, *sc, cm, row, x, y, z, v, gx, gy);
     if constexpr (CAMPAIGN) {
       q->lane_steps[e] = lane_steps + 1;
       ended = reached || row + 1 >= ln.max_steps;
@@ -498,19 +545,8 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
         r->flags = 3;
       }
       if constexpr (SCORED) {
-        if (ended) {  // L = row + 1 rows: the far branch and the orientation critic read the last ones
-          const float pf = sa.pf_far ? chain::path_far(x, y, sa.igx, sa.igy, sa.pf_scale) : sa.path;
-          const float po = row >= 1 ? chain::orientation(gx, gy, sa.x0, sa.y0, sa.lx, sa.ly, x, y) : 0.0f;
-          BatchTaskScore* o = sc->score + ln.task;
-          o->cost = chain::combine(sc->w_path, sc->w_slope, sc->w_speed, sc->w_obs, sc->w_orient, pf, sa.slope,
-                                   sa.speed, sa.obs, po);
-          o->terms[0] = pf;
-          o->terms[1] = sa.slope;
-          o->terms[2] = sa.speed;
-          o->terms[3] = sa.obs;
-          o->collisions = sa.col;
-          o->rows = row + 1;
-          o->length = sa.length;
+        if (ended) {
+          score_write(sc->score, ln.task, sa, *sc, row, x, y, gx, gy);
         } else {  // (the claim resets the record of a lane whose task ended)
           sa.lx = x;
           sa.ly = y;
@@ -589,6 +625,173 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
   }
 }
 
+// The result row of a run that ended: the state of the ending ingest (11 floats in mppi_state order),
+// its rows, the goal test's answer and the status.  The score row is the caller's.
+__device__ __forceinline__ void run_result(BatchTaskResult* r, const float* s, int steps, int reached, int status) {
+  r->x0 = s[0];
+  r->y0 = s[1];
+  r->h0x = s[2];
+  r->h0y = s[3];
+  r->h0z = s[4];
+  r->wl = s[5];
+  r->wr = s[6];
+  r->gx = s[7];
+  r->gy = s[8];
+  r->s1 = s[9];
+  r->s2 = s[10];
+  r->steps = steps;
+  r->reached = reached;
+  r->flags = status;
+}
+
+// The tracked form of the ingest (mppi_batch_step_tracked): the plain form's rule for which episode
+// takes the step and what its record receives, and around it the run.  Lane 0, in this order:
+//   a reset that finds an unfinished run with rows writes that run's result (abandoned: the state
+//   and the last row are the record's, which the previous ingest wrote) and begins a new run;
+//   the state that begins a run (a reset, or the first ingest after mppi_batch_set_episode) is its
+//   start: the accumulator starts over with the goal terms of that state, no row; a start inside the
+//   tolerance ends the run at once (steps 0, reached, a score row of zeros);
+//   any other ingested state is row rows: (x, y, z, the heading as given, v, w) with (v, w) the
+//   command the previous step left in the record and z the caller's, or the height of the episode's
+//   DEM at (x, y) by the rollout's own lookup (Dem::corners and bilinear, IEEE division); the row goes
+//   to the log (keep_log), into the chains (score_extend_row), then the goal test on the ingested
+//   state and the cap decide whether the run ends: the result and the score row (score_write) go to
+//   slot e * runs_per_episode + (the episode's run count) if there is one, and the count grows.
+// An ended episode is inactive for the step's other launches until its next reset, and keeps its
+// record, nominal sequence and step index.  done[e] reads the status of every set episode (0 for one
+// never set, so the whole array is written at every step).  The slot
+// depends on (e, run count) only: no atomic, and the active count is not touched.  One costmap gather
+// per row, and four DEM loads when z is null; no LDS, no waits.
+__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
+                                                                const int* __restrict__ is_set, const BatchTrack t) {
+  const int e = blockIdx.x;
+  BatchEpisode* ep = b.ep + e;
+  const bool set = is_set[e] != 0;
+  const bool on = set && (!io.mask || io.mask[e] != 0);
+  const bool reset = on && io.reset && io.reset[e] != 0;
+  if (threadIdx.x == 0) {
+    BatchTrackRec* tr = t.rec + e;
+    int ended = tr->ended;
+    if (on && (reset || !ended)) {
+      BatchTrackRec r = *tr;
+      int runs = t.runs[e];
+      const float* cm = t.cm;
+      const float* Z = t.Z;
+      if (b.scene) {
+        const BatchScene sl = b.scene->rec[e];
+        if (sl.cm >= 0) cm = b.scene->cms[sl.cm];
+        if (sl.dem >= 0) Z = b.scene->dem_z[sl.dem];
+      }
+      if (reset && !r.ended && !r.fresh && r.rows >= 1) {  // abandoned
+        if (runs < t.runs_per_episode) {
+          BatchRunResult* o = t.results + (size_t)e * t.runs_per_episode + runs;
+          const float last[11] = {ep->x0, ep->y0, ep->h0x, ep->h0y, ep->h0z, ep->wl, ep->wr, ep->gx, ep->gy, ep->s1, ep->s2};
+          run_result(&o->r, last, r.rows, 0, kRunAbandoned);
+          r.acc.lx = r.px;
+          r.acc.ly = r.py;
+          score_write(&o->s, 0, r.acc, t, r.rows - 1, last[0], last[1], r.gx, r.gy);
+        }
+        ++runs;
+      }
+      const float* s = io.states + (size_t)e * 11;
+      const float x = s[0], y = s[1], gx = s[7], gy = s[8];
+      ep->x0 = x;
+      ep->y0 = y;
+      ep->h0x = s[2];
+      ep->h0y = s[3];
+      ep->h0z = s[4];
+      ep->wl = s[5];
+      ep->wr = s[6];
+      ep->gx = gx;
+      ep->gy = gy;
+      ep->s1 = s[9];
+      ep->s2 = s[10];
+      episode_goal_fields(ep, x, y, gx, gy, b.horizon);
+      if (reset) {
+        ep->cur = 0;
+        ep->step = 0;
+        if (io.seeds) ep->seed = io.seeds[e];
+      }
+      const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
+      BatchRunResult* o = runs < t.runs_per_episode ? t.results + (size_t)e * t.runs_per_episode + runs : nullptr;
+      if (reset || r.fresh) {  // the run's start
+        BatchTrackRec z{};
+        z.acc.x0 = x;
+        z.acc.y0 = y;
+        z.acc.igx = ep->igx;
+        z.acc.igy = ep->igy;
+        z.acc.pf_scale = ep->pf_scale;
+        z.acc.pf_far = ep->pf_far;
+        z.acc.speed_on = ep->speed_on;
+        z.gx = gx;
+        z.gy = gy;
+        r = z;
+        if (t.keep_log) ep->steps_run = 0;
+        if (reached) {
+          if (o) {
+            run_result(&o->r, s, 0, 1, kRunReached);
+            o->s = BatchTaskScore{};
+          }
+          ++runs;
+          r.ended = kRunReached;
+        }
+      } else {  // row r.rows of the run
+        const int row = r.rows;
+        float z;
+        if (t.z) {
+          z = t.z[e];
+        } else {
+          Dem d;
+          d.init(Z, t.rows, t.grid, t.x_min, t.y_min, t.res);
+          bool unused = false;
+          float q[4];
+          d.corners<false>(x, y, q, unused);
+          z = bilinear<false>(x, y, q, d.rr<false>(), unused);
+        }
+        if (t.keep_log) {
+          if (row < b.log_cap) {
+            float* lg = b.log + ((size_t)e * b.log_cap + row) * 8;
+            lg[0] = x;
+            lg[1] = y;
+            lg[2] = z;
+            lg[3] = s[2];
+            lg[4] = s[3];
+            lg[5] = s[4];
+            lg[6] = r.v;
+            lg[7] = r.w;
+          }
+          ep->steps_run = min(row + 1, b.log_cap);
+        }
+        score_extend_row(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy);
+        r.rows = row + 1;
+        if (reached || row + 1 >= t.max_steps) {
+          if (o) {
+            run_result(&o->r, s, row + 1, reached ? 1 : 0, reached ? kRunReached : kRunCap);
+            score_write(&o->s, 0, r.acc, t, row, x, y, r.gx, r.gy);
+          }
+          ++runs;
+          r.ended = reached ? kRunReached : kRunCap;
+        } else {
+          r.px = r.acc.lx;
+          r.py = r.acc.ly;
+          r.acc.lx = x;
+          r.acc.ly = y;
+        }
+      }
+      ep->reached = r.ended == kRunReached ? 1 : 0;
+      *tr = r;
+      t.runs[e] = runs;
+      ended = r.ended;
+    }
+    ep->active = (on && !ended) ? 1 : 0;
+    if (t.done) t.done[e] = set ? ended : 0;
+  }
+  if (reset) {
+    float* u = b.unom + (size_t)e * 4 * b.H;
+    for (int j = (int)threadIdx.x; j < 4 * b.H; j += 64) u[j] = 0.0f;
+  }
+}
+
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
   // about four wave-units (two noise_waves iterations) per wave
   const int units = b.blocks * ((b.H + 1) >> 1) * 4;
@@ -617,13 +820,28 @@ hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t l
 }
 
 hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_ingest_kernel, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set);
+  void (*k)(const BatchArgs, const BatchIo, const int*) = mppi_batch_ingest_kernel;  // (the tracked form is an overload)
+  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set);
   return hipGetLastError();
 }
 
 hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
                                     hipStream_t st) {
   hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchIo>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, io);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_ingest_tracked(const BatchArgs& b, const BatchIo& io, const int* is_set, const BatchTrack& t,
+                                       hipStream_t st) {
+  void (*k)(const BatchArgs, const BatchIo, const int*, const BatchTrack) = mppi_batch_ingest_kernel;
+  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_step_tracked(const FinishArgs& f, const BatchArgs& b, const BatchTrackedIo& io,
+                                            size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchTrackedIo>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b,
+                     io);
   return hipGetLastError();
 }
 

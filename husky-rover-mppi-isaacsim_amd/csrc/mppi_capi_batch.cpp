@@ -76,6 +76,15 @@ struct mppi_batch {
   BatchScoredCampaign yard{};
   DeviceBuf<BatchScoreAcc> d_acc;     // [E]
   DeviceBuf<BatchTaskScore> d_score;  // [N]
+  // tracked device steps (mppi_batch_set_tracking): the yardstick and the caps as taken when tracking
+  // was set (the pointers and the scene are filled in by each step), the episodes' tracking records,
+  // their run counts and the results table
+  bool tracking = false;
+  BatchTrack trk{};
+  float trk_goal_tol = 0.0f;           // the goal test's tolerance (the untracked step reads no policy)
+  DeviceBuf<BatchTrackRec> d_track;    // [E]
+  DeviceBuf<int> d_runs;               // [E]
+  DeviceBuf<BatchRunResult> d_runres;  // [E][runs_per_episode]
 };
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
 static_assert(sizeof(mppi_critics) == sizeof(BatchCriticRow), "mppi_critics layout");
@@ -318,7 +327,10 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
 // One step of the set episodes from states in device memory: ingest, noise, a rollout per projection
 // in use, the finish's step form.  Enqueues and returns: no wait, no copy, no read of pinned memory.
 // Everything the host decides comes from its own bookkeeping (is_set, ep_var, variants, book).
-int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in) {
+// tracked (mppi_batch_step_tracked): the ingest and the finish are their tracked forms; z, done: the
+// step's two optional arrays.
+int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in, bool tracked = false,
+                      const float* z_dev = nullptr, int32_t* done_dev = nullptr) {
   mppi_ctx* c = b->c;
   const Plan pl = make_plan(c);
   bool any_set = false, any_var = false, use_proj[4] = {false, false, false, false};
@@ -347,12 +359,44 @@ int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in) {
   io.cmd = io_in.cmd;
   io.plan = io_in.plan;
   b->unwaited = true;
-  HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
+  if (tracked) {  // the records, the tables and the scene of this step around the yardstick as taken
+    BatchTrack t = b->trk;
+    t.rec = b->d_track;
+    t.runs = b->d_runs;
+    t.results = b->d_runres;
+    t.z = z_dev;
+    t.done = done_dev;
+    t.cm = c->cmap.cm;
+    t.cm_size = c->cmap.size;
+    t.hw = c->cmap.hw;
+    t.res_c = c->cmap.res;
+    t.Z = c->dem.Z;
+    t.rows = c->dem.rows;
+    t.grid = c->dem.cols;
+    t.x_min = c->dem.x_min;
+    t.y_min = c->dem.y_min;
+    t.res = c->dem.res;
+    z.goal_tol = b->trk_goal_tol;
+    HIP_TRY(launch_batch_ingest_tracked(z, io, b->d_set, t, c->stream));
+  } else {
+    HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
+  }
   HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
   for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
     if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-  HIP_TRY(launch_batch_finish_step(f, z, io, pl.fin_lds_bytes, c->stream));
+  if (tracked)
+    HIP_TRY(launch_batch_finish_step_tracked(f, z, BatchTrackedIo{io, b->d_track}, pl.fin_lds_bytes, c->stream));
+  else
+    HIP_TRY(launch_batch_finish_step(f, z, io, pl.fin_lds_bytes, c->stream));
   return MPPI_OK;
+}
+
+// The own-model runs and the task queue write the log, steps_last_run and the episode records that a
+// tracked run owns.
+int tracking_busy(const mppi_batch* b, const char* who) {
+  if (!b->tracking) return MPPI_OK;
+  return fail(MPPI_ESTATE, std::string(who) + ": tracking is set for the device steps (turn it off with "
+                                              "mppi_batch_set_tracking(b, NULL, 0, 0, 0, 0))");
 }
 
 // ---- the task queue ----
@@ -698,6 +742,10 @@ int mppi_batch_set_episode(mppi_batch* b, int32_t e, const mppi_state* start, ui
   HIP_TRY(hipMemcpyAsync(b->ep + e, &b->host[e], sizeof(BatchEpisode), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->unom + (size_t)e * 4 * b->H, 0, (size_t)4 * b->H * sizeof(float), c->stream));
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(b->d_set + e), 1, 1, c->stream));
+  BatchTrackRec fresh{};  // tracking: the episode's run begins at its next ingest; an unfinished one leaves no result
+  fresh.fresh = 1;
+  if (b->tracking)
+    HIP_TRY(hipMemcpyAsync(b->d_track + e, &fresh, sizeof(fresh), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return MPPI_OK;
 }
@@ -712,6 +760,7 @@ int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (int rc = campaign_busy(b, "batch_run")) return rc;
+  if (int rc = tracking_busy(b, "batch_run")) return rc;
   if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
   if (int rc_g = scene_geometry(b)) return rc_g;
@@ -721,15 +770,19 @@ int mppi_batch_run(mppi_batch* b, int32_t proj, int32_t n_steps, const mppi_loop
   return rc;
 }
 
-int mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io) {
+// mppi_batch_step_device and mppi_batch_step_tracked: one set of refusals.
+static int step_entry(mppi_batch* b, int32_t proj, const mppi_batch_io* io, const char* who, bool tracked,
+                      const float* z_dev, int32_t* done_dev) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
-  if (!io) return fail(MPPI_EINVAL, "batch_step_device: null io");
-  if (!io->states) return fail(MPPI_EINVAL, "batch_step_device: null states");
+  if (!io) return fail(MPPI_EINVAL, std::string(who) + ": null io");
+  if (!io->states) return fail(MPPI_EINVAL, std::string(who) + ": null states");
   if (proj != MPPI_PROJ_2D && proj != MPPI_PROJ_3D) return fail(MPPI_EINVAL, "proj must be 2 or 3");
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;  // (a host wait only while a resident server is running)
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
-  if (int rc = campaign_busy(b, "batch_step_device")) return rc;
+  if (int rc = campaign_busy(b, who)) return rc;
+  if (tracked && !b->tracking)
+    return fail(MPPI_ESTATE, std::string(who) + ": tracking is not set: call mppi_batch_set_tracking first");
   if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
   if (int rc_g = scene_geometry(b)) return rc_g;
@@ -737,9 +790,145 @@ int mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io)
   if (!pl.roles || pl.blocks != b->blocks)
     return fail(MPPI_ESTATE, "batch: the context does not run the role-split rollout plan (MPPI_ROLES=0)");
   HIP_TRY(hipSetDevice(c->device));
-  const int rc = batch_step_device(b, proj, *io);
+  const int rc = batch_step_device(b, proj, *io, tracked, z_dev, done_dev);
   if (rc == MPPI_EHIP) b->failed = true;
   return rc;
+}
+
+int mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io) {
+  return step_entry(b, proj, io, "batch_step_device", false, nullptr, nullptr);
+}
+
+int mppi_batch_step_tracked(mppi_batch* b, int32_t proj, const mppi_batch_io* io, const float* z_dev,
+                            int32_t* done_dev) {
+  return step_entry(b, proj, io, "batch_step_tracked", true, z_dev, done_dev);
+}
+
+static int after_wait(mppi_batch* b, int rc);
+
+int mppi_batch_set_tracking(mppi_batch* b, const mppi_batch_variant* yardstick, float goal_tol, int32_t max_steps,
+                            int32_t runs_per_episode, int32_t keep_log) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (max_steps < 0) return fail(MPPI_EINVAL, "batch_set_tracking: max_steps must be >= 0 (0 turns tracking off)");
+  if (max_steps > 0 && runs_per_episode < 1)
+    return fail(MPPI_EINVAL, "batch_set_tracking: runs_per_episode must be >= 1");
+  if (max_steps > 0 && !(goal_tol >= 0.0f)) return fail(MPPI_EINVAL, "batch_set_tracking: goal_tol must be >= 0");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (int rc = campaign_busy(b, "batch_set_tracking")) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // device steps in flight read the tables
+  b->tracking = false;
+  if (max_steps == 0) {
+    b->d_track.reset();
+    b->d_runs.reset();
+    b->d_runres.reset();
+    return MPPI_OK;
+  }
+  const size_t E = (size_t)b->E;
+  const size_t res_bytes = E * (size_t)runs_per_episode * sizeof(BatchRunResult);
+  const size_t log_bytes = keep_log ? E * (size_t)max_steps * 8 * sizeof(float) : 0;
+  if (b->d_track.grow(E * sizeof(BatchTrackRec)) || b->d_runs.grow(E * sizeof(int)) || b->d_runres.grow(res_bytes) ||
+      (keep_log && b->log.grow(log_bytes))) {
+    (void)hipGetLastError();
+    b->d_track.reset();
+    b->d_runs.reset();
+    b->d_runres.reset();
+    return fail(MPPI_EHIP, "batch_set_tracking: allocation of " + std::to_string(res_bytes) +
+                               " bytes of run results and " + std::to_string(log_bytes) + " bytes of log failed");
+  }
+  BatchTrackRec fresh{};  // every episode's run begins at its next ingest
+  fresh.fresh = 1;
+  const std::vector<BatchTrackRec> recs(E, fresh);
+  HIP_TRY(hipMemcpyAsync(b->d_track, recs.data(), E * sizeof(BatchTrackRec), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(b->d_runs, 0, E * sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(b->d_runres, 0, res_bytes, c->stream));
+  if (keep_log) {  // the log is laid out for max_steps rows per episode from here on: no episode has a row
+    b->log_cap = max_steps;
+    HIP_TRY(hipMemset2DAsync(&b->ep->steps_run, sizeof(BatchEpisode), 0, sizeof(int), E, c->stream));
+    for (BatchEpisode& r : b->host) r.steps_run = 0;
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));  // recs is pageable and dies here
+  const mppi_params& p = c->p;
+  BatchTrack& t = b->trk;
+  t = BatchTrack{};
+  t.max_steps = max_steps;
+  t.runs_per_episode = runs_per_episode;
+  t.keep_log = keep_log ? 1 : 0;
+  t.vmax = p.v_max_linear;  // the yardstick is taken here, as a scored list takes it
+  t.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+  t.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+  t.w_path = yardstick ? yardstick->w_path : p.w_path;
+  t.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+  t.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+  t.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  t.w_orient = c->crit.w_orientation;
+  b->trk_goal_tol = goal_tol;
+  b->tracking = true;
+  return MPPI_OK;
+}
+
+int mppi_batch_get_run_counts(mppi_batch* b, int32_t* counts) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (!counts) return fail(MPPI_EINVAL, "null argument");
+  if (!b->tracking)
+    return fail(MPPI_ESTATE, "batch_get_run_counts: tracking is not set: call mppi_batch_set_tracking first");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  static_assert(sizeof(int32_t) == sizeof(int), "run counts are int32");
+  hipError_t e = hipMemcpyAsync(counts, b->d_runs, (size_t)b->E * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return after_wait(b, fail(MPPI_EHIP, std::string("batch_get_run_counts: ") + hipGetErrorString(e)));
+  return after_wait(b, MPPI_OK);
+}
+
+int mppi_batch_get_runs(mppi_batch* b, int32_t e, int32_t first, int32_t count, mppi_state* states, int32_t* steps,
+                        int32_t* reached, int32_t* status, mppi_path_scores* out, int32_t* rows, double* length) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (!b->tracking) return fail(MPPI_ESTATE, "batch_get_runs: tracking is not set: call mppi_batch_set_tracking first");
+  const int R = b->trk.runs_per_episode;
+  if (first < 0 || count < 0 || (int64_t)first + count > R)
+    return fail(MPPI_EINVAL, "batch_get_runs: runs [" + std::to_string(first) + ", " +
+                                 std::to_string((int64_t)first + count) + ") outside the " + std::to_string(R) +
+                                 " result rows of an episode");
+  if (count == 0) return MPPI_OK;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<BatchRunResult> res((size_t)count);
+  hipError_t he = hipMemcpyAsync(res.data(), b->d_runres + ((size_t)e * R + first), (size_t)count * sizeof(BatchRunResult),
+                                 hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) return after_wait(b, fail(MPPI_EHIP, std::string("batch_get_runs: ") + hipGetErrorString(he)));
+  for (int32_t i = 0; i < count; ++i) {
+    const BatchTaskResult& r = res[(size_t)i].r;
+    const BatchTaskScore& s = res[(size_t)i].s;
+    if (states) {
+      mppi_state& st = states[i];
+      st.x = r.x0;
+      st.y = r.y0;
+      st.heading[0] = r.h0x;
+      st.heading[1] = r.h0y;
+      st.heading[2] = r.h0z;
+      st.left_wheel_speed = r.wl;
+      st.right_wheel_speed = r.wr;
+      st.goal_x = r.gx;
+      st.goal_y = r.gy;
+      st.std_dev_u1 = r.s1;
+      st.std_dev_u2 = r.s2;
+    }
+    if (steps) steps[i] = r.steps;
+    if (reached) reached[i] = r.reached;
+    if (status) status[i] = r.flags;
+    if (out && out->cost) out->cost[i] = s.cost;
+    if (out && out->terms) std::memcpy(out->terms + 4 * (size_t)i, s.terms, sizeof(s.terms));
+    if (out && out->collisions) out->collisions[i] = s.collisions;
+    if (rows) rows[i] = s.rows;
+    if (length) length[i] = s.length;
+  }
+  return after_wait(b, MPPI_OK);
 }
 
 // The two readers below wait for the stream: a HIP error of steps that mppi_batch_step_device
@@ -1056,6 +1245,13 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
     return MPPI_OK;
   }
   const mppi_params& p = c->p;
+  // a tracked run began on the device: its start and goal are in the episode's tracking record
+  std::vector<BatchTrackRec> trk;
+  if (!origins && b->tracking && b->trk.keep_log) {
+    trk.resize(E);
+    HIP_TRY(hipMemcpyAsync(trk.data(), b->d_track, E * sizeof(BatchTrackRec), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
   std::vector<ScoreGoal> goals(E);
   for (size_t e = 0; e < E; ++e) {
     mppi_state st{};
@@ -1064,6 +1260,11 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
       st.y = origins[e].y;
       st.goal_x = origins[e].goal_x;
       st.goal_y = origins[e].goal_y;
+    } else if (!trk.empty()) {
+      st.x = trk[e].acc.x0;
+      st.y = trk[e].acc.y0;
+      st.goal_x = trk[e].gx;
+      st.goal_y = trk[e].gy;
     } else {
       st.x = b->origin[e][0];
       st.y = b->origin[e][1];
@@ -1099,6 +1300,7 @@ static int set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks, boo
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
+  if (int rc = tracking_busy(b, "batch_set_tasks")) return rc;
   HIP_TRY(hipSetDevice(c->device));
   std::vector<TaskSpec> specs((size_t)n);
   for (int i = 0; i < n; ++i) {
@@ -1229,6 +1431,7 @@ int mppi_batch_run_tasks(mppi_batch* b, int32_t proj, int32_t n_steps, const mpp
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (b->tbook.empty()) return fail(MPPI_ESTATE, "batch_run_tasks: no task list: call mppi_batch_set_tasks first");
+  if (int rc = tracking_busy(b, "batch_run_tasks")) return rc;
   if (!c->dem.Z) return fail(MPPI_ESTATE, "no DEM: call mppi_set_dem first");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "no costmap: call mppi_set_costmap first");
   int s = b->tbook.mismatch(kSceneDem, b->book, dem_geom(c));

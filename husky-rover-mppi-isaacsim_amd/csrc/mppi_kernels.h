@@ -391,6 +391,58 @@ static_assert(sizeof(BatchIo) == 48, "BatchIo layout");
 hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st);
 hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
                                     hipStream_t st);
+// ---- tracked device steps (mppi_batch_set_tracking / _step_tracked) ----
+// The device step with the notion of a run: the ingest kernel's tracked form logs the row an ingested
+// state makes with the command the previous step wrote, extends the scorer's chains by it as the
+// scored campaign's advance lane does, tests the goal and the step cap, and writes the run's result
+// and score row when it ends; an ended episode stays inactive until its next reset.
+// One record per episode: read and written by lane 0 of workgroup e of the ingest only, but for
+// (v, w), which the tracked step finish stores behind a kernel boundary.
+struct BatchTrackRec {
+  BatchScoreAcc acc;  // the run's chains so far; acc.x0, acc.y0: the run's start
+  float gx, gy;       // the run's goal (the start state's)
+  float v, w;         // the command the episode's previous step wrote
+  float px, py;       // x, y of the row before the last one (acc.lx, acc.ly hold the last row's)
+  int rows;           // rows of the run so far
+  int ended;          // 0: running, 1: reached, 2: the step cap (what `done` reads)
+  int fresh;          // the run's start has not been ingested yet (mppi_batch_set_episode)
+  int pad;
+};
+static_assert(sizeof(BatchTrackRec) == 136, "BatchTrackRec layout");
+constexpr int kRunReached = 1, kRunCap = 2, kRunAbandoned = 3;  // BatchRunResult::r.flags, the run's status
+struct BatchRunResult {  // one row per (episode, run ordinal), zero until the run ends
+  BatchTaskResult r;     // the state at the ending ingest, steps, reached, flags = the status
+  BatchTaskScore s;      // zero for a run that took no step
+};
+static_assert(sizeof(BatchRunResult) == 96, "BatchRunResult layout");
+// The tracked ingest's own fourth kernel argument: the tables, the step's two optional arrays, the
+// yardstick as taken when tracking was set (the field names of BatchScoredCampaign: one scoring rule
+// serves both), and the context's costmap and DEM, which an episode's slots replace.
+struct BatchTrack {
+  BatchTrackRec* rec;    // [E]
+  int* runs;             // [E] runs ended per episode (may pass runs_per_episode: results were dropped)
+  BatchRunResult* results;  // [E][runs_per_episode]
+  const float* z;        // [E] or null: the plant's pose height; null: the episode's DEM at (x, y)
+  int* done;             // [E] or null: BatchTrackRec::ended of every set episode, 0 for one never set
+  int max_steps, runs_per_episode, keep_log;
+  int cm_size;
+  const float* cm;       // the context's costmap: an episode without a costmap slot
+  float hw, res_c;
+  float vmax, thr, pen;
+  float w_path, w_slope, w_speed, w_obs, w_orient;
+  const float* Z;        // the context's DEM: an episode without a DEM slot (z null only)
+  int rows, grid;
+  float x_min, y_min, res;
+};
+// The tracked step finish's third kernel argument: the io block and the records that take (v, w).
+struct BatchTrackedIo {
+  BatchIo io;
+  BatchTrackRec* rec;  // [E]
+};
+hipError_t launch_batch_ingest_tracked(const BatchArgs& b, const BatchIo& io, const int* is_set, const BatchTrack& t,
+                                       hipStream_t st);
+hipError_t launch_batch_finish_step_tracked(const FinishArgs& f, const BatchArgs& b, const BatchTrackedIo& io,
+                                            size_t lds, hipStream_t st);
 
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);

@@ -184,6 +184,13 @@ _PROTOS = {
     "mppi_batch_get_episode": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiState), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, _FP]),
     "mppi_batch_step_device": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchIo)]),
+    "mppi_batch_set_tracking": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.c_float, C.c_int32, C.c_int32,
+                                          C.c_int32]),
+    "mppi_batch_step_tracked": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiBatchIo), C.c_void_p, C.c_void_p]),
+    "mppi_batch_get_runs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MppiState),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(MppiPathScores), C.POINTER(C.c_int32), _DP]),
+    "mppi_batch_get_run_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mppi_batch_get_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "mppi_batch_get_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_batch_variant_default": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiLoopPolicy),
@@ -930,6 +937,7 @@ class Batch:
         h = C.c_void_p()
         _check(self.lib, self.lib.mppi_batch_create(engine.ctx, self.E, C.byref(h)), "mppi_batch_create")
         self.h = h
+        self.tracking = None    # set_tracking's arguments while tracking is set
 
     def set_episode(self, e, state: MppiState, seed, variant=-1, dem=-1, costmap=-1, trajectories=0):
         """Episode e starts at `state` with Philox key `seed` and runs with row `variant` of the table
@@ -1067,7 +1075,76 @@ class Batch:
             raise ValueError(f"{name} is on device {index}, the engine's is {self.engine.device}")
         return ptr
 
-    def step_device(self, states, mask=None, reset=None, seeds=None, cmd=None, plan=None, proj="3d"):
+    def set_tracking(self, yardstick=None, max_steps=None, runs_per_episode=1, keep_log=True, goal_tol=0.5):
+        """mppi_batch_set_tracking: from here on step_device tracks a run per set episode on the device:
+        it logs each ingested state beside the command before it, tests the goal (goal_tol) and the
+        step cap max_steps, scores the run with `yardstick` (MppiBatchVariant or dict whose weights,
+        collision_threshold and collision_penalty are used; default the engine's params) and writes
+        its result into one of the episode's runs_per_episode result rows; an ended episode idles
+        until its next reset.  keep_log=False: no log row is written (log() then has no rows).
+        Setting it again starts every run and count over.  runs() / run_counts() read the results."""
+        if max_steps is None:
+            raise ValueError("set_tracking needs max_steps, the step cap of a run (clear_tracking() turns tracking off)")
+        max_steps, runs_per_episode = int(max_steps), int(runs_per_episode)
+        if max_steps < 1:
+            raise ValueError(f"max_steps must be >= 1, got {max_steps} (clear_tracking() turns tracking off)")
+        if runs_per_episode < 1:
+            raise ValueError(f"runs_per_episode must be >= 1, got {runs_per_episode}")
+        if not float(goal_tol) >= 0:
+            raise ValueError(f"goal_tol must be >= 0, got {goal_tol!r}")
+        y = None if yardstick is None else C.byref(_as_variant(yardstick))
+        _check(self.lib, self.lib.mppi_batch_set_tracking(self.h, y, float(goal_tol), max_steps, runs_per_episode,
+                                                          1 if keep_log else 0), "mppi_batch_set_tracking")
+        self.tracking = dict(max_steps=max_steps, runs_per_episode=runs_per_episode, keep_log=bool(keep_log))
+
+    def clear_tracking(self):
+        """Turn tracking off and free its tables: step_device is the plain device step again."""
+        _check(self.lib, self.lib.mppi_batch_set_tracking(self.h, None, 0.0, 0, 0, 0), "mppi_batch_set_tracking")
+        self.tracking = None
+
+    def run_counts(self):
+        """mppi_batch_get_run_counts: int32 [E], the runs each episode has ended since tracking was set
+        (a count above runs_per_episode: results were dropped)."""
+        if not getattr(self, "tracking", None):
+            raise RuntimeError("run_counts: tracking is not set (set_tracking)")
+        counts = np.zeros(self.E, np.int32)
+        _check(self.lib, self.lib.mppi_batch_get_run_counts(self.h, counts.ctypes.data_as(C.POINTER(C.c_int32))),
+               "mppi_batch_get_run_counts")
+        return counts
+
+    def runs(self, e=None):
+        """mppi_batch_get_runs: the result rows of tracked runs.  e: an episode -> dict of arrays over its
+        runs_per_episode rows: run (the ordinal), state [R, 11] (mppi_state order, at the ending
+        ingest), steps, reached, status (0: no run has ended into the row, 1: reached, 2: the cap,
+        3: abandoned), cost, terms [R, 4], collisions, rows, length (float64).  e=None: every
+        episode's rows stacked, with an `episode` column (mppi_amd.batch.campaign_summary takes it)."""
+        tr = getattr(self, "tracking", None)
+        if not tr:
+            raise RuntimeError("runs: tracking is not set (set_tracking)")
+        R = tr["runs_per_episode"]
+        if e is None:
+            per = [self.runs(i) for i in range(self.E)]
+            out = {k: np.concatenate([p[k] for p in per]) for k in per[0]}
+            out["episode"] = np.repeat(np.arange(self.E, dtype=np.int32), R)
+            return out
+        e = int(e)
+        if not 0 <= e < self.E:
+            raise ValueError(f"episode {e} outside [0, {self.E})")
+        i32 = C.POINTER(C.c_int32)
+        st = (MppiState * R)()
+        out = dict(run=np.arange(R, dtype=np.int32), steps=np.zeros(R, np.int32), reached=np.zeros(R, np.int32),
+                   status=np.zeros(R, np.int32), cost=np.zeros(R, np.float32), terms=np.zeros((R, 4), np.float32),
+                   collisions=np.zeros(R, np.int32), rows=np.zeros(R, np.int32), length=np.zeros(R, np.float64))
+        sc = MppiPathScores(_fp(out["cost"]), _fp(out["terms"]), out["collisions"].ctypes.data_as(i32))
+        _check(self.lib, self.lib.mppi_batch_get_runs(
+            self.h, e, 0, R, st, out["steps"].ctypes.data_as(i32), out["reached"].ctypes.data_as(i32),
+            out["status"].ctypes.data_as(i32), C.byref(sc), out["rows"].ctypes.data_as(i32),
+            out["length"].ctypes.data_as(_DP)), "mppi_batch_get_runs")
+        out["state"] = np.frombuffer(bytes(st), dtype=np.float32).reshape(R, 11).copy()
+        return out
+
+    def step_device(self, states, mask=None, reset=None, seeds=None, cmd=None, plan=None, proj="3d", z=None,
+                    done=None):
         """mppi_batch_step_device: one step of every set episode from states held on the device, for a
         plant that is not the controller's own model.  Enqueues on the engine's stream and returns;
         it never synchronises, so the arrays are read and written in stream order and must stay
@@ -1082,6 +1159,12 @@ class Batch:
         torch.Tensor, __cuda_array_interface__, a DLPack producer), contiguous, on the engine's
         device.  cmd / plan not given are allocated as torch tensors (uninitialised: the rows of an
         episode that does not step are not written).  Returns (cmd, plan).
+
+        With tracking set (set_tracking) the call is mppi_batch_step_tracked: z: float32 [E] or None,
+        the plant's pose height of each rover (None: the episode's DEM at its x, y), the z of the
+        run's row; done: int32 [E], written at every step: 0 running (or never set), 1 reached, 2 the step
+        cap; allocated as a torch tensor when not given.  Returns (cmd, plan, done).  Without
+        tracking z and done are refused.
         """
         E, H = self.E, self.H
         io = MppiBatchIo()
@@ -1094,17 +1177,28 @@ class Batch:
             io.seeds = self._io_array(seeds, "seeds", ("u8", "i8"), (E,))
         if proj not in PROJ:
             raise ValueError(f"proj must be one of {sorted(map(str, PROJ))}, got {proj!r}")
-        if cmd is None or plan is None:
+        tracked = bool(getattr(self, "tracking", None))
+        if not tracked and (z is not None or done is not None):
+            raise ValueError("z and done belong to tracked steps: call set_tracking first")
+        z_ptr = None if z is None else self._io_array(z, "z", ("f4",), (E,))
+        if cmd is None or plan is None or (tracked and done is None):
             import torch
             device = torch.device("cuda", self.engine.device)
             if cmd is None:
                 cmd = torch.empty((E, 2), dtype=torch.float32, device=device)
             if plan is None:
                 plan = torch.empty((E, 4 * H + 12), dtype=torch.float32, device=device)
+            if tracked and done is None:
+                done = torch.empty((E,), dtype=torch.int32, device=device)   # (every entry is written)
         io.cmd = self._io_array(cmd, "cmd", ("f4",), (E, 2))
         io.plan = self._io_array(plan, "plan", ("f4",), (E, 4 * H + 12))
-        _check(self.lib, self.lib.mppi_batch_step_device(self.h, PROJ[proj], C.byref(io)), "mppi_batch_step_device")
-        return cmd, plan
+        if not tracked:
+            _check(self.lib, self.lib.mppi_batch_step_device(self.h, PROJ[proj], C.byref(io)), "mppi_batch_step_device")
+            return cmd, plan
+        done_ptr = self._io_array(done, "done", ("i4",), (E,))
+        _check(self.lib, self.lib.mppi_batch_step_tracked(self.h, PROJ[proj], C.byref(io), z_ptr, done_ptr),
+               "mppi_batch_step_tracked")
+        return cmd, plan, done
 
     def episode(self, e):
         """dict(state (MppiState), steps_total, steps_last_run, reached, u1, u2 (the next nominal sequence))."""

@@ -229,9 +229,15 @@ def campaign_summary(results, by=None):
     (its per-task dicts and the score arrays; see `campaign_results`).  by: one group key per task
     (task_variant, say); None: one group, keyed None.
 
+    results may also be the stacked rows of tracked runs (Batch.runs() / BatchStepper.runs(): a dict of
+    arrays with an `episode` column); `by` is then one key per episode (the variant each rover of
+    the simulator ran with, say), and the rows are taken through tracked_results first.
+
     Returns {key: dict(count, reached, collided (runs with at least one collision), mean=dict(cost,
     path, slope, speed, obstacle, length), std=the same fields)} in float64, the standard deviation
     the population's (numpy's default), keys in order of first appearance."""
+    if isinstance(results, dict):
+        results, by = tracked_results(results, by)
     results = list(results)
     keys = [None] * len(results) if by is None else list(by)
     if len(keys) != len(results):
@@ -249,6 +255,27 @@ def campaign_summary(results, by=None):
                       mean={f: float(np.mean(cols[f])) for f in SUMMARY_FIELDS},
                       std={f: float(np.std(cols[f])) for f in SUMMARY_FIELDS})
     return out
+
+
+RUN_STATUS = {0: "none", 1: "reached", 2: "cap", 3: "abandoned"}     # mppi_batch_get_runs' status
+
+
+def tracked_results(runs, by=None, abandoned=False):
+    """The stacked rows of tracked runs (Batch.runs(): dict of arrays with `episode`, `status`, `reached`,
+    `cost`, `terms`, `collisions`, `length`, ...) as (the per-run dicts campaign_summary takes, one group
+    key per run).  Rows no run has ended into (status 0) are left out, and abandoned runs (status 3:
+    cut short by a reset) unless abandoned=True; by: one key per episode (None: every run keyed None)."""
+    ep = np.asarray(runs["episode"], np.int64)
+    status = np.asarray(runs["status"], np.int64)
+    if by is not None:
+        by = list(by)
+        if len(ep) and int(ep.max()) >= len(by):
+            raise ValueError(f"{int(ep.max()) + 1} episodes but {len(by)} group keys")
+    keep = [i for i in range(len(ep)) if status[i] in ((1, 2, 3) if abandoned else (1, 2))]
+    out = [dict(episode=int(ep[i]), run=int(runs["run"][i]), status=int(status[i]), reached=bool(runs["reached"][i]),
+                loops=int(runs["steps"][i]), cost=runs["cost"][i], terms=runs["terms"][i],
+                collisions=runs["collisions"][i], length=runs["length"][i]) for i in keep]
+    return out, [None if by is None else by[int(ep[i])] for i in keep]
 
 
 def campaign_results(tasks, scores):

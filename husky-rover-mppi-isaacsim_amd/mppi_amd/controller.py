@@ -561,7 +561,7 @@ class MPPI_Controller:
         return batch
 
     def batch_stepper(self, episodes, seeds=None, variants=None, episode_variant=None, dems=None, costmaps=None,
-                      episode_dem=None, episode_costmap=None, episode_trajectories=None):
+                      episode_dem=None, episode_costmap=None, episode_trajectories=None, track=None):
         """E controllers for E rovers of an external, vectorised simulator (mppi_batch_step_device,
         DESIGN.md §3.7): the Isaac loop (visual_terrain_stack_full_terrain.py:466-515) with the poses
         kept in device tensors.  episodes: the E initial states (state dicts of mppi_amd.batch, or
@@ -572,10 +572,22 @@ class MPPI_Controller:
         Returns a BatchStepper: .step(states, mask=None, reset=None, seeds=None, proj="3d") ->
         (cmd [E, 2], plan [E, 4H + 12]) device tensors (Batch.step_device; the same two tensors at
         every step, so read them in stream order), .batch (the _lib.Batch) and .close().
+
+        track: None, or the arguments of _lib.Batch.set_tracking as a dict (max_steps, and optionally
+        yardstick, runs_per_episode, keep_log, goal_tol): a tracked stepper, whose runs are logged, tested
+        against goal and step cap, scored and ended on the device.  .step then takes z= and done= and
+        returns (cmd, plan, done); .runs() reads the results once the campaign is over.
         """
         states = [s if isinstance(s, _lib.MppiState) else to_mppi_state(s) for s in episodes]
-        return BatchStepper(self._open_batch(len(states), lambda: states, seeds, variants, episode_variant, dems, costmaps, episode_dem,
-                                             episode_costmap, episode_trajectories))
+        batch = self._open_batch(len(states), lambda: states, seeds, variants, episode_variant, dems, costmaps, episode_dem,
+                                 episode_costmap, episode_trajectories)
+        if track is not None:
+            try:
+                batch.set_tracking(**dict(track))
+            except Exception:
+                batch.close()
+                raise
+        return BatchStepper(batch)
 
     def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None,
                   variants=None, episode_variant=None, score=None, dems=None, costmaps=None, episode_dem=None,
@@ -718,11 +730,22 @@ class BatchStepper:
         self.batch = batch
         self.cmd = None
         self.plan = None
+        self.done = None
 
-    def step(self, states, mask=None, reset=None, seeds=None, proj="3d"):
-        """Batch.step_device with the stepper's own cmd / plan tensors; never synchronises."""
-        self.cmd, self.plan = self.batch.step_device(states, mask, reset, seeds, self.cmd, self.plan, proj)
-        return self.cmd, self.plan
+    def step(self, states, mask=None, reset=None, seeds=None, proj="3d", z=None, done=None):
+        """Batch.step_device with the stepper's own cmd / plan tensors; never synchronises.  A tracked
+        stepper (batch_stepper(track=...)) passes z and done through (done: the stepper's own tensor
+        when not given) and returns (cmd, plan, done)."""
+        if not getattr(self.batch, "tracking", None):
+            self.cmd, self.plan = self.batch.step_device(states, mask, reset, seeds, self.cmd, self.plan, proj, z, done)
+            return self.cmd, self.plan
+        self.cmd, self.plan, self.done = self.batch.step_device(states, mask, reset, seeds, self.cmd, self.plan, proj, z,
+                                                                self.done if done is None else done)
+        return self.cmd, self.plan, self.done
+
+    def runs(self, e=None):
+        """Batch.runs: the result rows of the tracked runs (synchronises)."""
+        return self.batch.runs(e)
 
     def close(self):
         self.batch.close()

@@ -654,6 +654,62 @@ typedef struct mppi_batch_io {   /* device pointers, on the batch context's devi
 } mppi_batch_io;
 int  mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io);
 
+/* ---- tracked device steps: the run of an external plant, kept on the device ----
+ * mppi_batch_step_device knows no run: a campaign in a simulator had to copy the states back every
+ * frame to test the goal, keep the paths and upload them again for mppi_batch_score.  With tracking
+ * set, every set episode carries a run that the ingest of mppi_batch_step_tracked logs, tests against
+ * its goal and step cap, scores and ends, with no host copy and no synchronisation.
+ * A run begins at mppi_batch_set_episode (with the first state ingested after it) or at a step with
+ * reset[e] != 0; the state that begins it is its start and gives no row.  Every later ingest of the
+ * run forms row n - 1 (n = 1, 2, ...) before anything else: x, y, z, heading[3] as given in
+ * states[e], then v, w, the command the previous step of the episode wrote (the pose after the
+ * command beside that command, as mppi_batch_run logs).  z is z_dev[e], the plant's pose height, or
+ * with z_dev NULL the height of the episode's DEM (its slot's, or the context's) at (x, y) by the
+ * rollout's lookup: the truncating cell index and the axis-swapped bilinear of projection_warp.py.
+ * The row extends the run's score, and with keep_log it goes to the episode's log, where
+ * mppi_batch_get_log and mppi_batch_score (origins NULL: the run's start and goal) read the current
+ * or most recent run.  Then the goal test !(|x - goal_x| > goal_tol || |y - goal_y| > goal_tol) on
+ * the ingested state and the cap decide: the run ends reached, or unreached when its rows reach
+ * max_steps.  A start inside the tolerance ends at once with steps 0, reached 1 and a score row of
+ * zeros.  A reset that finds an unfinished run with at least one row ends it as abandoned (its state
+ * and score are those of its last row); one without rows, and an unfinished run that
+ * mppi_batch_set_episode replaces, leave no result.
+ * The ending ingest writes the run's result into row r of the episode's result rows, r = the runs the
+ * episode has ended since tracking was set, if r < runs_per_episode, and counts the run either way.
+ * An ended episode does not step until its next reset: its rows of cmd and plan are not written and
+ * its state, nominal sequence and step index stay.  done_dev [E] (may be NULL) receives, for every
+ * set episode at every tracked step, 0 (running), 1 (reached) or 2 (the cap), and 0 for an episode
+ * never set; the plant's own reset logic reads it in stream order.
+ * The score row of a run is bit for bit what mppi_batch_score gives the same rows: cost, terms[4]
+ * (path, slope in the body form, speed, obstacle), collisions and rows, with origin = the run's start
+ * and goal, the episode's own costmap, the yardstick's weights, collision_threshold and
+ * collision_penalty (NULL: the context's params) and the context's w_orientation; the yardstick,
+ * w_orientation and v_max_linear are taken when tracking is set.  length: as mppi_batch_get_task_scores.
+ * Every step that is taken keeps the contract of mppi_batch_step_device.
+ * mppi_batch_set_tracking: max_steps >= 1 and runs_per_episode >= 1 turn tracking on (again: every run
+ * and count starts over) and allocate 136 bytes per episode and 96 per result row, and with
+ * keep_log != 0 max_steps log rows per episode (the log of an earlier mppi_batch_run is dropped);
+ * max_steps = 0 turns it off and frees them.  goal_tol: the goal test's tolerance (the untracked step
+ * takes no policy).  MPPI_EINVAL names the field; MPPI_ESTATE while a campaign is unfinished;
+ * MPPI_EHIP with the sizes when the allocation fails (tracking is then off).  While tracking is set
+ * mppi_batch_run, _set_tasks and _run_tasks answer MPPI_ESTATE: they write the same log and records.
+ * Synchronous. */
+int  mppi_batch_set_tracking(mppi_batch* b, const mppi_batch_variant* yardstick, float goal_tol, int32_t max_steps,
+                             int32_t runs_per_episode, int32_t keep_log);
+/* mppi_batch_step_device with the runs above: asynchronous in the same way, the same refusals, and
+ * MPPI_ESTATE without tracking set.  z_dev [E] float and done_dev [E] int32: device pointers or NULL. */
+int  mppi_batch_step_tracked(mppi_batch* b, int32_t proj, const mppi_batch_io* io, const float* z_dev,
+                             int32_t* done_dev);
+/* Result rows [first, first + count) of episode e (first + count <= runs_per_episode): the state at
+ * the ending ingest, steps, reached, status (0: no run has ended into this row, 1: reached, 2: the
+ * cap, 3: abandoned) and the score row (out's arrays of count, rows, length); any output may be NULL.
+ * One copy of count rows of 96 bytes, no kernel launch.  Synchronous.  MPPI_ESTATE without tracking. */
+int  mppi_batch_get_runs(mppi_batch* b, int32_t e, int32_t first, int32_t count, mppi_state* states, int32_t* steps,
+                         int32_t* reached, int32_t* status, mppi_path_scores* out, int32_t* rows, double* length);
+/* counts [E]: the runs each episode has ended since tracking was set; a count above runs_per_episode
+ * says that results were dropped.  One copy, no kernel launch.  Synchronous. */
+int  mppi_batch_get_run_counts(mppi_batch* b, int32_t* counts);
+
 /* HIP-event timing of the rollout kernel and of the combine/optimal-rollout
  * kernel, measured on the context stream around each launch.  enable: 0 off,
  * 1 rollout, finish and deferred-tail events (the host waits for the stream and

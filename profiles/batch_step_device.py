@@ -14,6 +14,11 @@ Three legs, alternated `--rounds` times in one process after a warm-up of each:
   host    the host-fed route: per step E set_episode calls (each zeroes the warm start and waits for
           the stream), run(1) and E episode() readbacks, `--host-steps` steps.
 
+  tracked (--tracked) the device leg with tracking set (mppi_batch_set_tracking): four more figures, the
+          step alone with keep_log on / off and z given / NULL (the DEM lookup), every run long enough
+          that no episode ends inside the timed region; the untracked step alone is timed beside them
+          in the same rounds.  Written to profiles/batch/step_tracked.json.
+
 Per-step wall time by perf_counter around work that ends in a stream synchronise.  `launch` is the
 time of one empty-ish kernel launch in the same job (a one-element torch add, enqueued 2 000 times,
 then one synchronise): what one more launch per step costs when launches are back to back.
@@ -40,6 +45,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--host-steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--tracked", action="store_true", help="time the tracked device step instead of the three legs")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-write", action="store_true")
     a = ap.parse_args()
@@ -93,7 +99,22 @@ def main():
         cmd = torch.zeros((E, 2), dtype=torch.float32, device="cuda")
         plan = torch.zeros((E, 4 * H + 12), dtype=torch.float32, device="cuda")
         one = torch.zeros(1, device="cuda")
+        zpose = torch.full((E,), 0.25, dtype=torch.float32, device="cuda")
+        done = torch.zeros(E, dtype=torch.int32, device="cuda")
     stream.synchronize()
+
+    def stat(v):
+        return dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2),
+                    all=[round(x, 2) for x in v])
+
+    def emit(res, name):
+        line = json.dumps(res)
+        print(line)
+        if not a.no_write:
+            out = a.out or os.path.join(ROOT, "profiles", "batch", name)
+            os.makedirs(os.path.dirname(out), exist_ok=True)
+            with open(out, "w") as f:
+                f.write(line + "\n")
 
     def leg_run():
         fill(batch)
@@ -118,6 +139,21 @@ def main():
         assert batch.episode(0)["steps_total"] == n
         return t / n * 1e6
 
+    def leg_tracked(keep_log, with_z):
+        fill(batch)
+        batch.set_tracking(max_steps=n + 1, keep_log=keep_log, goal_tol=0.5)
+        with torch.cuda.stream(stream):
+            states.copy_(torch.as_tensor(first), non_blocking=False)
+            stream.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                batch.step_device(states, cmd=cmd, plan=plan, z=zpose if with_z else None, done=done)
+            stream.synchronize()
+            t = time.perf_counter() - t0
+        assert batch.episode(0)["steps_total"] == n and not done.any().item()
+        batch.clear_tracking()
+        return t / n * 1e6
+
     def leg_host():
         fill(batch)
         cur = list(mstates)
@@ -138,6 +174,26 @@ def main():
             stream.synchronize()
             return (time.perf_counter() - t0) / m * 1e6
 
+    if a.tracked:
+        forms = dict(log_z=(True, True), log_dem=(True, False), nolog_z=(False, True), nolog_dem=(False, False))
+        leg_device(False)
+        for kw in forms.values():
+            leg_tracked(*kw)
+        rows = dict(device_alone=[], **{k: [] for k in forms})
+        for _ in range(a.rounds):
+            rows["device_alone"].append(leg_device(False))
+            for k, kw in forms.items():
+                rows[k].append(leg_tracked(*kw))
+        batch.close()
+        eng.close()
+        med = {k: statistics.median(v) for k, v in rows.items()}
+        res = dict(what="batch_step_tracked", K=a.K, H=H, E=E, steps=n, rounds=a.rounds, unit="us per batch step",
+                   **{k: stat(v) for k, v in rows.items()})
+        res["tracked_minus_device_alone_us"] = {k: round(med[k] - med["device_alone"], 2) for k in forms}
+        res["device_alone_spread_us"] = round(max(rows["device_alone"]) - min(rows["device_alone"]), 2)
+        emit(res, "step_tracked.json")
+        return
+
     # warm-up: every leg once at its timed shape (code objects loaded, the log grown, torch's kernels built)
     leg_run(), leg_device(True), leg_device(False), leg_host(), leg_launch()
     rows = dict(run_wall=[], run_event=[], device_plant=[], device_alone=[], host=[], launch=[])
@@ -152,10 +208,6 @@ def main():
     batch.close()
     eng.close()
 
-    def stat(v):
-        return dict(median=round(statistics.median(v), 2), min=round(min(v), 2), max=round(max(v), 2),
-                    all=[round(x, 2) for x in v])
-
     res = dict(what="batch_step_device", K=a.K, H=H, E=E, steps=n, host_steps=a.host_steps, rounds=a.rounds,
                unit="us per batch step", **{k: stat(v) for k, v in rows.items()})
     med = {k: statistics.median(v) for k, v in rows.items()}
@@ -164,13 +216,7 @@ def main():
     res["run_spread_us"] = round(max(rows["run_wall"]) - min(rows["run_wall"]), 2)
     res["episode_steps_per_s"] = {k: round(E / med[k] * 1e6) for k in ("run_wall", "device_plant", "device_alone",
                                                                          "host")}
-    line = json.dumps(res)
-    print(line)
-    if not a.no_write:
-        out = a.out or os.path.join(ROOT, "profiles", "batch", "step_device.json")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        with open(out, "w") as f:
-            f.write(line + "\n")
+    emit(res, "step_device.json")
 
 
 if __name__ == "__main__":

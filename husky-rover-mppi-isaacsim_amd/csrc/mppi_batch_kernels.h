@@ -24,6 +24,11 @@
 // step the notion of a run: it logs the row an ingested state makes, extends the scorer's chains by it
 // (the scored form's own device functions), tests the goal and the step cap and writes the run's
 // result; the finish kernel's tracked step form keeps the command for the next row.
+//
+// The wheel forms (mppi_batch_set_wheel_log / _set_score_options): instantiations of the finish and of
+// the tracked ingest whose own argument block ends in BatchWheelOpts.  They also log the row's wheel
+// contacts beside the row, extend the slope chain over them (score_extend_row_x) and feed the path
+// metrics (mppi_path_metrics.h).  The host picks them only when an option is on.
 #pragma once
 
 // The normals of every active episode's current step, [blocks][2][H][256] per episode, addressed as
@@ -276,14 +281,34 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // Row `row` of a path enters the accumulator: (x, y, z) and v, what the log row holds; (gx, gy) the
 // path's goal, cm its costmap.  The one statement of the rule for the scored campaign's advance lane
 // and the tracked ingest.  Y: the block that carries the yardstick (BatchScoredCampaign, BatchTrack).
-template <class Y>
-__device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
-                                                 float y, float z, float v, float gx, float gy) {
+// WX (the wheel forms), wheels: the slope chain reads the row's wheel contacts cw (left | right) in place of
+// the body waypoint: slope_one on both wheels against the previous even contacts in wa, the larger value
+// (the scorer's WHEELS slope wave; critics_warp.py:168-218), in the same order over the even rows.  (wa and
+// cw go in by reference and the choice as a flag: behind a pointer that may be null they stayed in memory.)
+template <bool WX, class Y>
+__device__ __forceinline__ void score_extend_row_x(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
+                                                   float y, float z, float v, float gx, float gy, bool wheels,
+                                                   BatchWheelAcc& wa, const float (&cw)[6]) {
   if (!sa.pf_far) {  // the near branch: the term of row - 1 enters now that this row exists
     if (row >= 1) sa.path = sa.path + sa.path_pend;
     sa.path_pend = chain::path_near(x, y, gx, gy);
   }
-  if ((row & 1) == 0) {  // an even row s: its term (rows s - 2 and s) waits for row s + 1
+  if (WX && wheels) {
+    if ((row & 1) == 0) {
+      const float l3[3] = {cw[0], cw[1], cw[2]}, r3[3] = {cw[3], cw[4], cw[5]};
+      if (row >= 2) {
+        const float ls = chain::slope_one(wa.pl, l3), rs = chain::slope_one(wa.pr, r3);
+        sa.slope_pend = (ls > rs) ? ls : rs;
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        wa.pl[i] = l3[i];
+        wa.pr[i] = r3[i];
+      }
+    } else if (row >= 3) {
+      sa.slope = sa.slope + sa.slope_pend;
+    }
+  } else if ((row & 1) == 0) {  // an even row s: its term (rows s - 2 and s) waits for row s + 1
     const float c3[3] = {x, y, z};
     if (row >= 2) sa.slope_pend = chain::slope_one(sa.pe, c3);
     sa.pe[0] = x;
@@ -306,6 +331,13 @@ __device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const Y& yd,
     sa.sy = y;
     sa.sz = z;
   }
+}
+template <class Y>
+__device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
+                                                 float y, float z, float v, float gx, float gy) {
+  BatchWheelAcc none{};
+  const float no_contacts[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  score_extend_row_x<false>(sa, yd, cm, row, x, y, z, v, gx, gy, false, none, no_contacts);
 }
 
 // The score row of a path that ended with row `row` at (x, y), into table[index]: L = row + 1 rows; the
@@ -343,18 +375,39 @@ __device__ __forceinline__ const BatchIo* io_of(const BatchTrackedIo& t) { retur
 template <class... Q>
 __device__ __forceinline__ BatchTrackRec* track_of(const Q&...) { return nullptr; }
 __device__ __forceinline__ BatchTrackRec* track_of(const BatchTrackedIo& t) { return t.rec; }
+// the wheel forms: the form's own block, then BatchWheelOpts
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelRun&) { return nullptr; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelCampaign& w) { return &w.q; }
+__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelScored& w) { return &w.s.q; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchWheelRun&) { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchWheelCampaign&) { return nullptr; }
+__device__ __forceinline__ const BatchIo* io_of(const BatchWheelScored&) { return nullptr; }
+__device__ __forceinline__ const BatchScoredCampaign* scored_of(const BatchWheelScored& w) { return &w.s; }
+template <class... Q>
+__device__ __forceinline__ const BatchWheelOpts* wheels_of(const Q&...) { return nullptr; }
+__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelRun& w) { return &w.x; }
+__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelCampaign& w) { return &w.x; }
+__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelScored& w) { return &w.x; }
 template <class... Queue>
 __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
                                                                          const Queue... queue) {
   static_assert(sizeof...(Queue) <= 1, "at most the one queue, or the one io block");
-  constexpr bool SCORED = (std::is_same<Queue, BatchScoredCampaign>::value || ...);
-  constexpr bool CAMPAIGN = (std::is_same<Queue, BatchCampaign>::value || ...) || SCORED;
+  // WX: a wheel form (mppi_batch_set_wheel_log / _set_score_options): the advance lane also reads row 0 of
+  // the optimal rollout's wheel contacts (floats 4H + 6 .. 4H + 11 of the finish output), logs them beside
+  // the row, extends the slope chain in its wheel form and the path metrics by them
+  constexpr bool WX = ((std::is_same<Queue, BatchWheelRun>::value || std::is_same<Queue, BatchWheelCampaign>::value ||
+                        std::is_same<Queue, BatchWheelScored>::value) || ...);
+  constexpr bool SCORED =
+      ((std::is_same<Queue, BatchScoredCampaign>::value || std::is_same<Queue, BatchWheelScored>::value) || ...);
+  constexpr bool CAMPAIGN =
+      ((std::is_same<Queue, BatchCampaign>::value || std::is_same<Queue, BatchWheelCampaign>::value) || ...) || SCORED;
   constexpr bool TRACKED = (std::is_same<Queue, BatchTrackedIo>::value || ...);
   constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...) || TRACKED;
-  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP ? 1 : 0),
-                "the third argument is a BatchCampaign, a BatchScoredCampaign, a BatchIo or a BatchTrackedIo");
+  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP || WX ? 1 : 0),
+                "the third argument is a BatchCampaign, a BatchScoredCampaign, a BatchIo, a BatchTrackedIo or a wheel form");
   const BatchCampaign* q = queue_of(queue...);
   const BatchScoredCampaign* sc = scored_of(queue...);
+  const BatchWheelOpts* wx = wheels_of(queue...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
@@ -371,6 +424,12 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   if constexpr (SCORED) {
     sa = sc->acc[e];
     cm = sc->cm;
+  }
+  BatchWheelAcc wa{};   // WX, SCORED: the lane's previous even contacts and its metrics state, loaded here too
+  PathMetricsAcc ma{};
+  if constexpr (WX && SCORED) {
+    if (wx->wacc) wa = wx->wacc[e];
+    if (wx->macc) ma = wx->macc[e];
   }
   FinishArgs f = f_in;
   const int H = f.H, E = 2 * H + 2;
@@ -495,6 +554,16 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
     bool log_row = row < (CAMPAIGN ? ln.max_steps : b.log_cap);
     if constexpr (SCORED) log_row = log_row && q->log != nullptr;
+    float cw[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // WX: left_wheel_sim[0] | right_wheel_sim[0]
+    if constexpr (WX) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) cw[i] = ld(4 * H + 6 + i);
+      if (log_row && wx->wlog) {  // the row of the same index in the parallel array
+        float* wl = wx->wlog + (CAMPAIGN ? (size_t)ln.log_base + row : (size_t)e * b.log_cap + row) * 6;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wl[i] = cw[i];
+      }
+    }
     if (log_row) {
       float* lg = CAMPAIGN ? q->log + ((size_t)ln.log_base + row) * 8 : b.log + ((size_t)e * b.log_cap + row) * 8;
       lg[0] = x;
@@ -523,7 +592,12 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     ep->steps_run = row + 1;
     const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
     // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
-    if constexpr (SCORED) score_extend_row(sa, *sc, cm, row, x, y, z, v, gx, gy);
+    if constexpr (SCORED && WX) {
+      score_extend_row_x<true>(sa, *sc, cm, row, x, y, z, v, gx, gy, wx->wacc != nullptr, wa, cw);
+      if (wx->macc) metrics_row(ma, row, x, y, z);
+    } else if constexpr (SCORED) {
+      score_extend_row(sa, *sc, cm, row, x, y, z, v, gx, gy);
+    }
     if constexpr (CAMPAIGN) {
       q->lane_steps[e] = lane_steps + 1;
       ended = reached || row + 1 >= ln.max_steps;
@@ -547,10 +621,16 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
       if constexpr (SCORED) {
         if (ended) {
           score_write(sc->score, ln.task, sa, *sc, row, x, y, gx, gy);
+          if constexpr (WX)
+            if (wx->macc) wx->metrics[ln.task] = ma.m;
         } else {  // (the claim resets the record of a lane whose task ended)
           sa.lx = x;
           sa.ly = y;
           sc->acc[e] = sa;
+          if constexpr (WX) {  // (row 0 of the next task starts both over)
+            if (wx->wacc) wx->wacc[e] = wa;
+            if (wx->macc) wx->macc[e] = ma;
+          }
         }
       }
     } else if (reached) {
@@ -662,8 +742,44 @@ __device__ __forceinline__ void run_result(BatchTaskResult* r, const float* s, i
 // never set, so the whole array is written at every step).  The slot
 // depends on (e, run count) only: no atomic, and the active count is not touched.  One costmap gather
 // per row, and four DEM loads when z is null; no LDS, no waits.
-__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
-                                                                const int* __restrict__ is_set, const BatchTrack t) {
+//
+// WX (mppi_batch_ingest_kernel's BatchWheelTrack overload; mppi_batch_set_wheel_log / _set_score_options
+// before tracking was set): the row also gets its wheel contacts, formed from the ingested pose by the
+// rollout's own rule (wheel_contacts below) on the episode's DEM; they go to the wheel log beside the row,
+// into the slope chain's wheel form and, with (x, y, z), into the path metrics, whose row is written
+// beside the run's score row.
+//
+// The contacts of a pose (projection_warp.py:331-347; oracle/mppi_ref.py rollout3d :306-315 with `cur`
+// the row's heading as given): q = the corners of the cell of (x, y), n = normal_on_grid(q),
+// c = cross(n, heading), r = (off c.x, off c.y), left = (x + r.x, y + r.y, Z[cell]), right the same with
+// -r; truncating cell index with clamping, IEEE / and sqrtf (Dem's <false> forms).
+__device__ __forceinline__ void wheel_contacts(const Dem& d, float x, float y, float hx, float hy, float hz, float off,
+                                               float (&cw)[6]) {
+  bool unused = false;
+  float q[4];
+  d.corners<false>(x, y, q, unused);
+  const float hr = (-d.res) / 2.0f;
+  const float vx = hr * (((q[1] - q[0]) - q[2]) + q[3]);
+  const float vy = hr * (((q[2] - q[0]) - q[1]) + q[3]);
+  const float vz = d.res * d.res;
+  const float norm = sqrtf((vx * vx + vy * vy) + vz * vz);
+  const float nx = vx / norm, ny = vy / norm, nz = vz / norm;
+  const float rx = off * (ny * hz - nz * hy);
+  const float ry = off * (nz * hx - nx * hz);
+  int i, j;
+  cw[0] = x + rx;
+  cw[1] = y + ry;
+  d.cell<false>(cw[0], cw[1], i, j, unused);
+  cw[2] = d.at(j, i);
+  cw[3] = x - rx;
+  cw[4] = y - ry;
+  d.cell<false>(cw[3], cw[4], i, j, unused);
+  cw[5] = d.at(j, i);
+}
+
+template <bool WX>
+__device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo& io, const int* __restrict__ is_set,
+                                               const BatchTrack& t, const BatchWheelOpts* wx) {
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
   const bool set = is_set[e] != 0;
@@ -690,6 +806,8 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
           r.acc.lx = r.px;
           r.acc.ly = r.py;
           score_write(&o->s, 0, r.acc, t, r.rows - 1, last[0], last[1], r.gx, r.gy);
+          if constexpr (WX)
+            if (wx->macc) wx->metrics[(size_t)e * t.runs_per_episode + runs] = wx->macc[e].m;
         }
         ++runs;
       }
@@ -731,6 +849,8 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
           if (o) {
             run_result(&o->r, s, 0, 1, kRunReached);
             o->s = BatchTaskScore{};
+            if constexpr (WX)
+              if (wx->macc) wx->metrics[(size_t)e * t.runs_per_episode + runs] = PathMetrics{0.0, 0.0, 0.0, 0.0};
           }
           ++runs;
           r.ended = kRunReached;
@@ -762,12 +882,38 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
           }
           ep->steps_run = min(row + 1, b.log_cap);
         }
-        score_extend_row(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy);
+        if constexpr (WX) {
+          float cw[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+          const bool log_w = wx->wlog && t.keep_log && row < b.log_cap;
+          if (log_w || wx->wacc) {
+            Dem d;
+            d.init(Z, t.rows, t.grid, t.x_min, t.y_min, t.res);
+            wheel_contacts(d, x, y, s[2], s[3], s[4], wx->off, cw);
+          }
+          if (log_w) {
+            float* wl = wx->wlog + ((size_t)e * b.log_cap + row) * 6;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) wl[i] = cw[i];
+          }
+          BatchWheelAcc wa{};
+          if (wx->wacc) wa = wx->wacc[e];
+          score_extend_row_x<true>(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy, wx->wacc != nullptr, wa, cw);
+          if (wx->wacc) wx->wacc[e] = wa;
+          if (wx->macc) {
+            PathMetricsAcc ma = wx->macc[e];
+            metrics_row(ma, row, x, y, z);
+            wx->macc[e] = ma;
+          }
+        } else {
+          score_extend_row(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy);
+        }
         r.rows = row + 1;
         if (reached || row + 1 >= t.max_steps) {
           if (o) {
             run_result(&o->r, s, row + 1, reached ? 1 : 0, reached ? kRunReached : kRunCap);
             score_write(&o->s, 0, r.acc, t, row, x, y, r.gx, r.gy);
+            if constexpr (WX)
+              if (wx->macc) wx->metrics[(size_t)e * t.runs_per_episode + runs] = wx->macc[e].m;
           }
           ++runs;
           r.ended = reached ? kRunReached : kRunCap;
@@ -790,6 +936,16 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
     float* u = b.unom + (size_t)e * 4 * b.H;
     for (int j = (int)threadIdx.x; j < 4 * b.H; j += 64) u[j] = 0.0f;
   }
+}
+
+__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
+                                                                const int* __restrict__ is_set, const BatchTrack t) {
+  tracked_ingest<false>(b, io, is_set, t, nullptr);
+}
+
+__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
+                                                                const int* __restrict__ is_set, const BatchWheelTrack w) {
+  tracked_ingest<true>(b, io, is_set, w.t, &w.x);
 }
 
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
@@ -867,5 +1023,32 @@ hipError_t launch_batch_finish_scored(const FinishArgs& f, const BatchArgs& b, c
                                       size_t lds, hipStream_t st) {
   hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchScoredCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f,
                      b, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelRun& w, size_t lds,
+                                      hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelRun>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_campaign_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelCampaign& w,
+                                               size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f,
+                     b, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_finish_scored_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelScored& w,
+                                             size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelScored>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b,
+                     w);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_ingest_tracked_wheels(const BatchArgs& b, const BatchIo& io, const int* is_set,
+                                              const BatchWheelTrack& t, hipStream_t st) {
+  void (*k)(const BatchArgs, const BatchIo, const int*, const BatchWheelTrack) = mppi_batch_ingest_kernel;
+  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set, t);
   return hipGetLastError();
 }

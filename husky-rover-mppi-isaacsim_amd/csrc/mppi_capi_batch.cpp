@@ -13,7 +13,9 @@
 #include "mppi.h"
 #include "mppi_batch_scene.h"
 #include "mppi_batch_tasks.h"
+#include "mppi_batch_wheels.h"
 #include "mppi_ctx.h"
+#include "mppi_path_metrics.h"
 #include "mppi_score.h"
 
 using namespace mppi;
@@ -85,7 +87,21 @@ struct mppi_batch {
   DeviceBuf<BatchTrackRec> d_track;    // [E]
   DeviceBuf<int> d_runs;               // [E]
   DeviceBuf<BatchRunResult> d_runres;  // [E][runs_per_episode]
+  // wheel contacts and path metrics of executed paths (mppi_batch_set_wheel_log / _set_score_options): the
+  // options as last set, read by the next run, list or tracking; then what each of those took, and the
+  // tables, which exist only while their option is on
+  BatchWheelBook wbook;                   // decides (mppi_batch_wheels.h); the rest is the tables it names
+  DeviceBuf<float> wlog;                  // [E][log_cap][6], parallel to log: exists iff wbook.log_wheels()
+  DeviceBuf<float> twlog;                 // the arena's parallel array, [rows of the arena][6]
+  DeviceBuf<BatchWheelAcc> d_wacc;        // [E] a scored list's lanes
+  DeviceBuf<PathMetricsAcc> d_macc;       // [E]
+  DeviceBuf<PathMetrics> d_metrics;       // [N] beside d_score
+  DeviceBuf<BatchWheelAcc> d_twacc;       // [E] tracked runs
+  DeviceBuf<PathMetricsAcc> d_tmacc;      // [E]
+  DeviceBuf<PathMetrics> d_runmetrics;    // [E][runs_per_episode] beside d_runres
 };
+static_assert(sizeof(mppi_path_metrics) == sizeof(PathMetrics), "mppi_path_metrics layout");
+static_assert(kWheelSlopeWheels == MPPI_SLOPE_WHEELS && kWheelSlopeBody == MPPI_SLOPE_BODY, "mppi_slope_mode");
 static_assert(sizeof(mppi_batch_variant) == sizeof(BatchVariant), "mppi_batch_variant layout");
 static_assert(sizeof(mppi_critics) == sizeof(BatchCriticRow), "mppi_critics layout");
 static_assert(sizeof(SceneRecord) == sizeof(BatchScene), "SceneRecord is BatchScene field for field");
@@ -288,6 +304,14 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   const size_t log_need = (size_t)b->E * n_steps * 8 * sizeof(float);
   rc = grow(b->log, log_need, c->stream);
   if (rc) return rc;
+  BatchWheelBook wb = b->wbook;  // (the book takes the run once its array stands)
+  if (wb.take_run().wlog) {      // the parallel array, 24 bytes per log row
+    rc = grow(b->wlog, (size_t)b->E * n_steps * 6 * sizeof(float), c->stream);
+    if (rc) return rc;
+  } else {
+    b->wlog.reset();
+  }
+  b->wbook = wb;
   b->log_cap = n_steps;
   HIP_TRY(hipMemcpyAsync(b->ep, b->host.data(), (size_t)b->E * sizeof(BatchEpisode), hipMemcpyHostToDevice,
                          c->stream));
@@ -301,6 +325,8 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   z.log = b->log;
   z.log_cap = b->log_cap;
   z.scene = b->book.need_table() ? b->d_tab.get() : nullptr;  // null: the kernels of the batch without scenes
+  BatchWheelRun wr{};  // the wheel log on: the finish form that also stores the contacts
+  wr.x.wlog = b->wlog;
   const int every = pol.check_every > 0 ? pol.check_every : 16;
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
   for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
@@ -311,7 +337,10 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
       // returns at once); without variants that is the run's projection alone
       for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
         if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-      HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
+      if (b->wbook.log_wheels())
+        HIP_TRY(launch_batch_finish_wheels(f, z, wr, pl.fin_lds_bytes, c->stream));
+      else
+        HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     done += m;
@@ -377,7 +406,19 @@ int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in, bool 
     t.y_min = c->dem.y_min;
     t.res = c->dem.res;
     z.goal_tol = b->trk_goal_tol;
-    HIP_TRY(launch_batch_ingest_tracked(z, io, b->d_set, t, c->stream));
+    const WheelTables& wt = b->wbook.tracking();
+    if (wt.any()) {
+      BatchWheelTrack w{};
+      w.t = t;
+      w.x.wlog = wt.wlog ? b->wlog.get() : nullptr;
+      w.x.wacc = wt.wacc ? b->d_twacc.get() : nullptr;
+      w.x.macc = wt.metrics ? b->d_tmacc.get() : nullptr;
+      w.x.metrics = wt.metrics ? b->d_runmetrics.get() : nullptr;
+      w.x.off = c->p.wheel_offset;
+      HIP_TRY(launch_batch_ingest_tracked_wheels(z, io, b->d_set, w, c->stream));
+    } else {
+      HIP_TRY(launch_batch_ingest_tracked(z, io, b->d_set, t, c->stream));
+    }
   } else {
     HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
   }
@@ -458,6 +499,11 @@ void task_list_clear(mppi_batch* b) {
   b->res.clear();
   b->campaign = mppi_batch::kNotStarted;
   b->scored = false;
+  b->wbook.clear_list();  // and its tables go with it
+  b->twlog.reset();
+  b->d_wacc.reset();
+  b->d_macc.reset();
+  b->d_metrics.reset();
 }
 
 BatchCampaign campaign_args(mppi_batch* b) {
@@ -534,6 +580,17 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
   sq.cm_size = c->cmap.size;
   sq.hw = c->cmap.hw;
   sq.res_c = c->cmap.res;
+  // a list set with the wheel log, the wheel slope mode or the metrics on: the wheel forms of the finish
+  const WheelTables& lt = b->wbook.list();
+  const bool wheel_form = lt.any();
+  BatchWheelOpts wx{};
+  wx.wlog = lt.wlog ? b->twlog.get() : nullptr;
+  wx.wacc = lt.wacc ? b->d_wacc.get() : nullptr;
+  wx.macc = lt.metrics ? b->d_macc.get() : nullptr;
+  wx.metrics = lt.metrics ? b->d_metrics.get() : nullptr;
+  wx.off = c->p.wheel_offset;
+  const BatchWheelCampaign wq{q, wx};
+  const BatchWheelScored wsq{sq, wx};
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
   if (b->campaign == mppi_batch::kNotStarted) {
     // the first fill: every lane empty and counted active, then one claim each
@@ -547,6 +604,11 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
     if (b->scored) {  // no task has a score yet; the claim resets the lanes' records
       HIP_TRY(hipMemsetAsync(b->d_score, 0, (size_t)N * sizeof(BatchTaskScore), c->stream));
       HIP_TRY(hipMemsetAsync(b->d_acc, 0, E * sizeof(BatchScoreAcc), c->stream));
+      if (lt.wacc) HIP_TRY(hipMemsetAsync(b->d_wacc, 0, E * sizeof(BatchWheelAcc), c->stream));
+      if (lt.metrics) {
+        HIP_TRY(hipMemsetAsync(b->d_macc, 0, E * sizeof(PathMetricsAcc), c->stream));
+        HIP_TRY(hipMemsetAsync(b->d_metrics, 0, (size_t)N * sizeof(PathMetrics), c->stream));
+      }
       HIP_TRY(launch_batch_claim_scored(z, sq, c->stream));
     } else {
       HIP_TRY(launch_batch_claim(z, q, c->stream));
@@ -561,7 +623,11 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
       HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
       for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
         if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-      if (b->scored)
+      if (wheel_form && b->scored)
+        HIP_TRY(launch_batch_finish_scored_wheels(f, z, wsq, pl.fin_lds_bytes, c->stream));
+      else if (wheel_form)
+        HIP_TRY(launch_batch_finish_campaign_wheels(f, z, wq, pl.fin_lds_bytes, c->stream));
+      else if (b->scored)
         HIP_TRY(launch_batch_finish_scored(f, z, sq, pl.fin_lds_bytes, c->stream));
       else
         HIP_TRY(launch_batch_finish_campaign(f, z, q, pl.fin_lds_bytes, c->stream));
@@ -588,15 +654,17 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
 int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::vector<const float*>& cmaps,
                const std::vector<int64_t>& base_rows, const float* log, const int32_t* lengths, int len_step,
                int stride, const mppi_batch_variant* yardstick, mppi_path_scores* out, int32_t* rows,
-               const char* who) {
+               const char* who, const float* wlog = nullptr, mppi_path_metrics* metrics = nullptr) {
   mppi_ctx* c = b->c;
   const mppi_params& p = c->p;
   const size_t E = goals.size();
   // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps][base rows]
+  // (wlog: the wheel log beside `log`, the slope term in its wheel form; metrics: [E] host rows, the path
+  // metrics of each log, a second small launch), then [metrics]
   const size_t bg = up16(E * sizeof(ScoreGoal)), bn = up16(E * 4), bt = E * 16, bp = up16(cmaps.size() * sizeof(float*)),
-               bb = base_rows.size() * sizeof(int64_t);
+               bb = up16(base_rows.size() * sizeof(int64_t)), bm = metrics ? E * sizeof(PathMetrics) : 0;
   DeviceBuf<char> dbuf;
-  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp + bb));
+  HIP_TRY(dbuf.alloc(bg + bn * 3 + bt + bp + bb + bm));
   char* buf = dbuf;
   ScoreGoal* d_goals = (ScoreGoal*)buf;
   float* d_cost = (float*)(buf + bg);
@@ -605,9 +673,11 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
   int32_t* d_rows = (int32_t*)(buf + bg + bn + bt + bn);
   const float** d_cmaps = (const float**)(buf + bg + bn + bt + bn + bn);
   int64_t* d_base = (int64_t*)(buf + bg + bn + bt + bn + bn + bp);
+  PathMetrics* d_met = (PathMetrics*)(buf + bg + bn + bt + bn + bn + bp + bb);
   ScoreArgs a;
   std::memset(&a, 0, sizeof(a));
   a.log = log;
+  a.lw = wlog;
   a.goals = d_goals;
   a.lengths = lengths;  // the device table's own counters, len_step ints apart
   a.len_step = len_step;
@@ -634,9 +704,14 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
   hipError_t e = hipMemcpyAsync(d_goals, goals.data(), E * sizeof(ScoreGoal), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && bp)
     e = hipMemcpyAsync(d_cmaps, cmaps.data(), cmaps.size() * sizeof(float*), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && bb) e = hipMemcpyAsync(d_base, base_rows.data(), bb, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && bb)
+    e = hipMemcpyAsync(d_base, base_rows.data(), base_rows.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
   int rc = MPPI_OK;
   if (e == hipSuccess) rc = run_score(c, a);
+  if (e == hipSuccess && rc == MPPI_OK && metrics) {
+    e = launch_log_metrics(log, lengths, len_step, a.base_row, stride, (int64_t)E, d_met, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(metrics, d_met, bm, hipMemcpyDeviceToHost, c->stream);
+  }
   if (e == hipSuccess && rc == MPPI_OK && out->cost) e = hipMemcpyAsync(out->cost, d_cost, E * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && rc == MPPI_OK && out->terms) e = hipMemcpyAsync(out->terms, d_terms, E * 16, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && rc == MPPI_OK && out->collisions) e = hipMemcpyAsync(out->collisions, d_col, E * 4, hipMemcpyDeviceToHost, c->stream);
@@ -820,31 +895,52 @@ int mppi_batch_set_tracking(mppi_batch* b, const mppi_batch_variant* yardstick, 
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));  // device steps in flight read the tables
   b->tracking = false;
+  b->wbook.clear_tracking();
+  b->d_twacc.reset();
+  b->d_tmacc.reset();
+  b->d_runmetrics.reset();
   if (max_steps == 0) {
     b->d_track.reset();
     b->d_runs.reset();
     b->d_runres.reset();
     return MPPI_OK;
   }
+  // the options as they stand (mppi_batch_set_wheel_log / _set_score_options): tables only for those on
+  BatchWheelBook wb = b->wbook;  // (the book takes tracking once the tables stand)
+  const WheelTables wt = wb.take_tracking(keep_log != 0);
+  const bool wheels_log = wt.wlog, slope_wheels = wt.wacc, metrics = wt.metrics;
   const size_t E = (size_t)b->E;
   const size_t res_bytes = E * (size_t)runs_per_episode * sizeof(BatchRunResult);
   const size_t log_bytes = keep_log ? E * (size_t)max_steps * 8 * sizeof(float) : 0;
   if (b->d_track.grow(E * sizeof(BatchTrackRec)) || b->d_runs.grow(E * sizeof(int)) || b->d_runres.grow(res_bytes) ||
-      (keep_log && b->log.grow(log_bytes))) {
+      (keep_log && b->log.grow(log_bytes)) || (wheels_log && b->wlog.grow(E * (size_t)max_steps * 6 * sizeof(float))) ||
+      (slope_wheels && b->d_twacc.grow(E * sizeof(BatchWheelAcc))) ||
+      (metrics && (b->d_tmacc.grow(E * sizeof(PathMetricsAcc)) ||
+                   b->d_runmetrics.grow(E * (size_t)runs_per_episode * sizeof(PathMetrics))))) {
     (void)hipGetLastError();
     b->d_track.reset();
     b->d_runs.reset();
     b->d_runres.reset();
+    b->d_twacc.reset();
+    b->d_tmacc.reset();
+    b->d_runmetrics.reset();
     return fail(MPPI_EHIP, "batch_set_tracking: allocation of " + std::to_string(res_bytes) +
                                " bytes of run results and " + std::to_string(log_bytes) + " bytes of log failed");
   }
+  b->wbook = wb;          // the tables stand
   BatchTrackRec fresh{};  // every episode's run begins at its next ingest
   fresh.fresh = 1;
   const std::vector<BatchTrackRec> recs(E, fresh);
   HIP_TRY(hipMemcpyAsync(b->d_track, recs.data(), E * sizeof(BatchTrackRec), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->d_runs, 0, E * sizeof(int), c->stream));
   HIP_TRY(hipMemsetAsync(b->d_runres, 0, res_bytes, c->stream));
+  if (slope_wheels) HIP_TRY(hipMemsetAsync(b->d_twacc, 0, E * sizeof(BatchWheelAcc), c->stream));
+  if (metrics) {
+    HIP_TRY(hipMemsetAsync(b->d_tmacc, 0, E * sizeof(PathMetricsAcc), c->stream));
+    HIP_TRY(hipMemsetAsync(b->d_runmetrics, 0, E * (size_t)runs_per_episode * sizeof(PathMetrics), c->stream));
+  }
   if (keep_log) {  // the log is laid out for max_steps rows per episode from here on: no episode has a row
+    if (!wheels_log) b->wlog.reset();
     b->log_cap = max_steps;
     HIP_TRY(hipMemset2DAsync(&b->ep->steps_run, sizeof(BatchEpisode), 0, sizeof(int), E, c->stream));
     for (BatchEpisode& r : b->host) r.steps_run = 0;
@@ -1226,18 +1322,29 @@ int mppi_batch_set_episode_trajectories(mppi_batch* b, int32_t e, int64_t num_tr
   return push_scene(b, e, before);
 }
 
-int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
-                     mppi_path_scores* out, int32_t* rows) {
+static int slope_mode_check(int32_t slope_mode, const char* who) {
+  if (slope_mode == MPPI_SLOPE_BODY || slope_mode == MPPI_SLOPE_WHEELS) return MPPI_OK;
+  return fail(MPPI_EINVAL, std::string(who) + ": slope_mode must be MPPI_SLOPE_WHEELS or MPPI_SLOPE_BODY");
+}
+
+// mppi_batch_score and mppi_batch_score_ex: the slope term in its body form, or (wheels) over the wheel
+// log's two contact paths; metrics [E] or null.
+static int batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins, bool wheels,
+                       mppi_path_scores* out, int32_t* rows, mppi_path_metrics* metrics) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
   if (!out) return fail(MPPI_EINVAL, "null argument");
   mppi_ctx* c = b->c;
   if (int rc_q = quiesce(c)) return rc_q;
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score: no costmap: call mppi_set_costmap first");
+  if (wheels && !b->wbook.can_score_wheels((bool)b->log))
+    return fail(MPPI_ESTATE, "batch_score: MPPI_SLOPE_WHEELS needs the wheel log: call mppi_batch_set_wheel_log(b, 1) "
+                             "before the run (a log row alone has no wheel contacts)");
   if (int rc_g = scene_geometry(b)) return rc_g;
   HIP_TRY(hipSetDevice(c->device));
   const size_t E = (size_t)b->E;
   if (!b->log) {  // no run yet: no episode has a row
+    if (metrics) std::memset(metrics, 0, E * sizeof(mppi_path_metrics));
     if (out->cost) std::memset(out->cost, 0, E * 4);
     if (out->terms) std::memset(out->terms, 0, E * 16);
     if (out->collisions) std::memset(out->collisions, 0, E * 4);
@@ -1286,7 +1393,84 @@ int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const m
     }
   }
   return score_logs(b, goals, cmaps, {}, b->log, &b->ep->steps_run, (int)(sizeof(BatchEpisode) / sizeof(int32_t)),
-                    b->log_cap, yardstick, out, rows, "batch_score");
+                    b->log_cap, yardstick, out, rows, "batch_score", wheels ? b->wlog.get() : nullptr, metrics);
+}
+
+int mppi_batch_score(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                     mppi_path_scores* out, int32_t* rows) {
+  return batch_score(b, yardstick, origins, false, out, rows, nullptr);
+}
+
+int mppi_batch_score_ex(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                        int32_t slope_mode, mppi_path_scores* out, int32_t* rows, mppi_path_metrics* metrics) {
+  if (int rc = slope_mode_check(slope_mode, "batch_score_ex")) return rc;
+  return batch_score(b, yardstick, origins, slope_mode == MPPI_SLOPE_WHEELS, out, rows, metrics);
+}
+
+int mppi_batch_set_wheel_log(mppi_batch* b, int32_t enable) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  switch (b->wbook.set_wheel_log(enable != 0, b->campaign == mppi_batch::kUnfinished, b->tracking)) {
+    case kWheelCampaign: return campaign_busy(b, "batch_set_wheel_log");
+    case kWheelTracking: return tracking_busy(b, "batch_set_wheel_log");
+    default: return MPPI_OK;
+  }
+}
+
+int mppi_batch_set_score_options(mppi_batch* b, int32_t slope_mode, int32_t metrics) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  switch (b->wbook.set_score_options(slope_mode, metrics != 0, b->campaign == mppi_batch::kUnfinished, b->tracking)) {
+    case kWheelSlopeMode: return slope_mode_check(slope_mode, "batch_set_score_options");
+    case kWheelCampaign: return campaign_busy(b, "batch_set_score_options");
+    case kWheelTracking: return tracking_busy(b, "batch_set_score_options");
+    default: return MPPI_OK;
+  }
+}
+
+int mppi_batch_get_wheel_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows6) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "wheel log range out of bounds");
+  if (count > 0 && !rows6) return fail(MPPI_EINVAL, "null argument");
+  if (!b->wbook.log_wheels())
+    return fail(MPPI_ESTATE, "batch_get_wheel_log: the log has no wheel log beside it: call mppi_batch_set_wheel_log(b, 1) "
+                             "before the run or before tracking is set");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  BatchEpisode& r = b->host[e];
+  hipError_t he = hipMemcpyAsync(&r, b->ep + e, sizeof(BatchEpisode), hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) return after_wait(b, fail(MPPI_EHIP, std::string("batch_get_wheel_log: ") + hipGetErrorString(he)));
+  if ((int64_t)first + count > r.steps_run)
+    return after_wait(b, fail(MPPI_EINVAL, "wheel log range beyond the steps of the last run"));
+  if (count > 0) {
+    he = hipMemcpyAsync(rows6, b->wlog + ((size_t)e * b->log_cap + first) * 6, (size_t)count * 6 * sizeof(float),
+                        hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) return after_wait(b, fail(MPPI_EHIP, std::string("batch_get_wheel_log: ") + hipGetErrorString(he)));
+  }
+  return after_wait(b, MPPI_OK);
+}
+
+int mppi_batch_get_run_metrics(mppi_batch* b, int32_t e, int32_t first, int32_t count, mppi_path_metrics* metrics) {
+  if (int rc = batch_episode(b, e)) return rc;
+  if (!b->tracking || !b->wbook.tracking().metrics)
+    return fail(MPPI_ESTATE, "batch_get_run_metrics: tracking was not set with the metrics on: call "
+                             "mppi_batch_set_score_options(b, slope_mode, 1), then mppi_batch_set_tracking");
+  const int R = b->trk.runs_per_episode;
+  if (first < 0 || count < 0 || (int64_t)first + count > R)
+    return fail(MPPI_EINVAL, "batch_get_run_metrics: runs [" + std::to_string(first) + ", " +
+                                 std::to_string((int64_t)first + count) + ") outside the " + std::to_string(R) +
+                                 " result rows of an episode");
+  if (count == 0) return MPPI_OK;
+  if (!metrics) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  hipError_t he = hipMemcpyAsync(metrics, b->d_runmetrics + ((size_t)e * R + first), (size_t)count * sizeof(PathMetrics),
+                                 hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+  if (he != hipSuccess) return after_wait(b, fail(MPPI_EHIP, std::string("batch_get_run_metrics: ") + hipGetErrorString(he)));
+  return after_wait(b, MPPI_OK);
 }
 
 // mppi_batch_set_tasks and mppi_batch_set_tasks_scored: one list, one set of checks.  scored: the
@@ -1327,9 +1511,16 @@ static int set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks, boo
   // (a list that keeps no log has no arena, and gives an earlier list's back: no kernel is in flight)
   const size_t log_bytes = keep_log ? ((size_t)fresh.total_rows() + (size_t)fresh.max_cap()) * 8 * sizeof(float) : 0;
   if (!keep_log) b->tlog.reset();
+  // the options as they stand (mppi_batch_set_wheel_log / _set_score_options): tables only for those on
+  // (task_list_clear dropped the old list's tables)
+  BatchWheelBook wb = b->wbook;  // (the book takes the list once the tables stand)
+  const WheelTables lt = wb.take_list(scored, keep_log);
+  const bool wheels_log = lt.wlog, slope_wheels = lt.wacc, metrics = lt.metrics;
   if (b->d_tasks.grow(N * sizeof(BatchTask)) || b->d_res.grow(N * sizeof(BatchTaskResult)) ||
       b->d_lane.grow(E * sizeof(BatchLane)) || b->d_count.grow((E + 1) * sizeof(int)) ||
-      (keep_log && b->tlog.grow(log_bytes)) ||
+      (keep_log && b->tlog.grow(log_bytes)) || (wheels_log && b->twlog.grow(log_bytes / 8 * 6)) ||
+      (slope_wheels && b->d_wacc.grow(E * sizeof(BatchWheelAcc))) ||
+      (metrics && (b->d_macc.grow(E * sizeof(PathMetricsAcc)) || b->d_metrics.grow(N * sizeof(PathMetrics)))) ||
       (scored && (b->d_acc.grow(E * sizeof(BatchScoreAcc)) || b->d_score.grow(N * sizeof(BatchTaskScore))))) {
     (void)hipGetLastError();
     return fail(MPPI_EHIP, "tasks: allocation of the tables of " + std::to_string(n) + " tasks and a log arena of " +
@@ -1362,11 +1553,13 @@ static int set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks, boo
   HIP_TRY(hipMemcpyAsync(b->d_tasks, dev.data(), N * sizeof(BatchTask), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(b->d_res, 0, N * sizeof(BatchTaskResult), c->stream));
   if (scored) HIP_TRY(hipMemsetAsync(b->d_score, 0, N * sizeof(BatchTaskScore), c->stream));
+  if (metrics) HIP_TRY(hipMemsetAsync(b->d_metrics, 0, N * sizeof(PathMetrics), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // dev is pageable and dies here
   b->tbook = fresh;
   b->tasks.assign(tasks, tasks + n);
   b->res.assign(N, BatchTaskResult{});
   b->scored = scored;
+  b->wbook = wb;
   if (scored) {  // the yardstick is taken here (as score_logs takes it when it scores a log)
     const mppi_params& p = c->p;
     BatchScoredCampaign& y = b->yard;
@@ -1501,8 +1694,48 @@ int mppi_batch_get_task_log(mppi_batch* b, int32_t i, int32_t first, int32_t cou
   return MPPI_OK;
 }
 
-int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
-                           mppi_path_scores* out, int32_t* rows) {
+int mppi_batch_get_task_wheel_log(mppi_batch* b, int32_t i, int32_t first, int32_t count, float* rows6) {
+  if (int rc = batch_task(b, i)) return rc;
+  if (first < 0 || count < 0) return fail(MPPI_EINVAL, "wheel log range out of bounds");
+  if (count > 0 && !rows6) return fail(MPPI_EINVAL, "null argument");
+  if ((int64_t)first + count > b->res[i].steps)
+    return fail(MPPI_EINVAL, "task " + std::to_string(i) + ": wheel log range beyond the " +
+                                 std::to_string(b->res[i].steps) + " steps the task has taken");
+  if (!b->wbook.list().wlog)
+    return fail(MPPI_ESTATE, "batch_get_task_wheel_log: the task list keeps no wheel log: call "
+                             "mppi_batch_set_wheel_log(b, 1) before the list is set (and keep its log)");
+  if (count == 0) return MPPI_OK;
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(rows6, b->twlog + ((size_t)b->tbook.base(i) + first) * 6, (size_t)count * 6 * sizeof(float),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+int mppi_batch_get_task_metrics(mppi_batch* b, int32_t first, int32_t count, mppi_path_metrics* metrics) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  if (b->tbook.empty() || !b->scored || !b->wbook.list().metrics)
+    return fail(MPPI_ESTATE, "batch_get_task_metrics: the task list was not set scored with the metrics on: call "
+                             "mppi_batch_set_score_options(b, slope_mode, 1), then mppi_batch_set_tasks_scored");
+  if (first < 0 || count < 0 || (int64_t)first + count > b->tbook.size())
+    return fail(MPPI_EINVAL, "batch_get_task_metrics: tasks [" + std::to_string(first) + ", " +
+                                 std::to_string((int64_t)first + count) + ") outside the list of " +
+                                 std::to_string(b->tbook.size()) + " tasks");
+  if (count == 0) return MPPI_OK;
+  if (!metrics) return fail(MPPI_EINVAL, "null argument");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(metrics, b->d_metrics + first, (size_t)count * sizeof(PathMetrics), hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPPI_OK;
+}
+
+static int batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins, bool wheels,
+                             mppi_path_scores* out, int32_t* rows, mppi_path_metrics* metrics) {
   if (!b) return fail(MPPI_EINVAL, "null batch");
   if (!out) return fail(MPPI_EINVAL, "null argument");
   mppi_ctx* c = b->c;
@@ -1510,6 +1743,9 @@ int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, c
   if (b->failed) return fail(MPPI_ESTATE, "batch: a HIP error ended an earlier run");
   if (b->tbook.empty()) return fail(MPPI_ESTATE, "batch_score_tasks: no task list: call mppi_batch_set_tasks first");
   if (!b->tbook.keeps_log()) return fail(MPPI_ESTATE, "batch_score_tasks: the task list keeps no log (keep_log = 0)");
+  if (wheels && !b->wbook.list().wlog)
+    return fail(MPPI_ESTATE, "batch_score_tasks: MPPI_SLOPE_WHEELS needs the wheel log: call "
+                             "mppi_batch_set_wheel_log(b, 1) before the list is set (a log row alone has no wheel contacts)");
   if (!c->cmap.cm) return fail(MPPI_ESTATE, "batch_score_tasks: no costmap: call mppi_set_costmap first");
   const int s = b->tbook.mismatch(kSceneCostmap, b->book, costmap_geom(c));
   if (s >= 0)
@@ -1542,7 +1778,19 @@ int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, c
   }
   // lengths: the result table's own step counts (0 for a task that has not ended)
   return score_logs(b, goals, cmaps, base, b->tlog, &b->d_res->steps, (int)(sizeof(BatchTaskResult) / sizeof(int32_t)),
-                    b->tbook.max_cap(), yardstick, out, rows, "batch_score_tasks");
+                    b->tbook.max_cap(), yardstick, out, rows, "batch_score_tasks", wheels ? b->twlog.get() : nullptr,
+                    metrics);
+}
+
+int mppi_batch_score_tasks(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                           mppi_path_scores* out, int32_t* rows) {
+  return batch_score_tasks(b, yardstick, origins, false, out, rows, nullptr);
+}
+
+int mppi_batch_score_tasks_ex(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                              int32_t slope_mode, mppi_path_scores* out, int32_t* rows, mppi_path_metrics* metrics) {
+  if (int rc = slope_mode_check(slope_mode, "batch_score_tasks_ex")) return rc;
+  return batch_score_tasks(b, yardstick, origins, slope_mode == MPPI_SLOPE_WHEELS, out, rows, metrics);
 }
 
 }  // extern "C"

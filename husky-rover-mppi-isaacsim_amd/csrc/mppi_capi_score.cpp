@@ -235,4 +235,25 @@ int mppi_get_score_ms(mppi_ctx* c, double* ms) {
   return MPPI_OK;
 }
 
+int mppi_detmath_atan2(mppi_ctx* c, int64_t n, const double* y, const double* x, double* dm, double* dev) {
+  if (!c) return fail(MPPI_EINVAL, "null context");
+  if (n < 0 || n > ((int64_t)1 << 28)) return fail(MPPI_EINVAL, "detmath_atan2: n must be in [0, 2^28]");
+  if (n == 0) return MPPI_OK;
+  if (!y || !x || !dm || !dev) return fail(MPPI_EINVAL, "null argument");
+  if (int rc_q = quiesce(c)) return rc_q;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = (size_t)n * sizeof(double);
+  DeviceBuf<double> buf;
+  HIP_TRY(buf.alloc(4 * bytes));
+  double* d = buf;
+  hipError_t e = hipMemcpyAsync(d, y, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + n, x, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_atan2_probe(d, d + n, n, d + 2 * n, d + 3 * n, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dm, d + 2 * n, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dev, d + 3 * n, bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(MPPI_EHIP, std::string("detmath_atan2: ") + hipGetErrorString(e));
+  return MPPI_OK;
+}
+
 }  // extern "C"

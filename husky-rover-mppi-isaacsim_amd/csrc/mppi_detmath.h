@@ -13,10 +13,17 @@
 // offset = 4 n).  One block feeds two rollout-steps of one trajectory.
 #pragma once
 
+// Plain-host inclusion is supported for everything in this file: without __HIPCC__ no HIP header is
+// read and MPPI_HD is an always-inline host function (clang: the vector forms use ext_vector_type).  The
+// native checks under tests/native (near1_recip_check, noise_pack_check, path_metrics_check) build it so.
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #define MPPI_HD __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#define MPPI_HD inline __attribute__((always_inline))
+#endif
+#include <stdint.h>
 
 namespace mppi {
 
@@ -336,6 +343,42 @@ MPPI_HD void noise_block(uint64_t seed, uint64_t n, uint64_t k, float* a1, float
                              (uint32_t)seed, (uint32_t)(seed >> 32));
   dm_box_muller(r.x, r.y, a1, a2);
   dm_box_muller(r.z, r.w, b1, b2);
+}
+
+// ------------------------------------------------------------------ atan2 (float64)
+// The arctangent of the path metrics (mppi_path_metrics.h; MPPI_isaac.py:246 np.arctan2), DEFINED as a
+// fixed sequence of IEEE float64 + - * / sqrt, so the device and the numpy restatement
+// (mppi_amd/batch.py dm_atan2) agree bit for bit:
+//   t = min(|y|, |x|) / max(|y|, |x|) in [0, 1] (0 for y = x = 0);
+//   three half-angle steps t <- t / (1 + sqrt(1 + t t)): t = tan(atan(t0) / 8) <= tan(pi / 32) < 0.0985;
+//   the odd series t - t^3 / 3 + ... - t^23 / 23 (12 terms, the first left out is < 3e-26 relative),
+//   Horner in z = t t from the last coefficient, then times t, then times 8 (exact);
+//   |y| > |x|: pi/2 - r;  x < 0: pi - r;  y < 0: -r.
+// Finite arguments; a signed zero counts as +0 (atan2(-0, -1) is pi here).  The coefficients are the
+// correctly rounded quotients 1 / (2 k + 1), which the compiler and Python both form as IEEE divisions.
+MPPI_HD double dm_atan2(double y, double x) {
+  const double ay = y < 0.0 ? -y : y, ax = x < 0.0 ? -x : x;
+  const double mn = ay < ax ? ay : ax, mx = ay < ax ? ax : ay;
+  double t = mx > 0.0 ? mn / mx : 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t = t / (1.0 + __builtin_sqrt(1.0 + t * t));
+  const double z = t * t;
+  double p = -1.0 / 23.0;
+  p = p * z + 1.0 / 21.0;
+  p = p * z + -1.0 / 19.0;
+  p = p * z + 1.0 / 17.0;
+  p = p * z + -1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + -1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + -1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + -1.0 / 3.0;
+  p = p * z + 1.0;
+  double r = (t * p) * 8.0;
+  if (ay > ax) r = 1.5707963267948966 - r;
+  if (x < 0.0) r = 3.141592653589793 - r;
+  return y < 0.0 ? -r : r;
 }
 
 }  // namespace mppi

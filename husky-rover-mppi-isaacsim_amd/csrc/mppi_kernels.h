@@ -443,6 +443,56 @@ hipError_t launch_batch_ingest_tracked(const BatchArgs& b, const BatchIo& io, co
                                        hipStream_t st);
 hipError_t launch_batch_finish_step_tracked(const FinishArgs& f, const BatchArgs& b, const BatchTrackedIo& io,
                                             size_t lds, hipStream_t st);
+// ---- wheel contacts and path metrics of executed paths (mppi_batch_set_wheel_log /
+// _set_score_options) ----
+// Opt-in: a batch that turns none of them on launches the kernels above with the arguments above.  With
+// one on, the host picks the forms below, whose third (ingest: fourth) kernel argument is the form's own
+// block followed by BatchWheelOpts; every table is allocated only while its option is on.
+//   wlog     the wheel-contact log, parallel to the log: row n of a path's log has its contacts
+//            (lx, ly, lz, rx, ry, rz) in row n of the same index here.  Own model: floats 4H + 6 .. 4H + 11
+//            of the step's finish output (row 0 of left_wheel_sim / right_wheel_sim); tracked: formed by
+//            the ingest from the ingested pose and the episode's DEM (projection_warp.py:331-347).
+//   wacc     the two previous even contacts of each lane: with it the online slope chain is the wheel
+//            form (chain::slope_one on both wheels, the larger value), else the body form.
+//   macc / metrics  the online state of compute_path_metrics (mppi_path_metrics.h) per lane, and the
+//            result rows beside the score rows ([n] tasks, or [E][runs_per_episode]).
+struct BatchWheelAcc {
+  float pl[3], pr[3];  // the contacts of the last even row
+};
+static_assert(sizeof(BatchWheelAcc) == 24, "BatchWheelAcc layout");
+struct PathMetricsAcc;
+struct PathMetrics;
+struct BatchWheelOpts {
+  float* wlog;           // null: no wheel log (a list or tracking that keeps no log has none either)
+  BatchWheelAcc* wacc;   // [E] or null
+  PathMetricsAcc* macc;  // [E] or null
+  PathMetrics* metrics;  // with macc
+  float off;             // mppi_params wheel_offset (the tracked ingest forms the contacts)
+  int pad;
+};
+struct BatchWheelRun {  // the plain finish form's (mppi_batch_run with the wheel log on)
+  BatchWheelOpts x;
+};
+struct BatchWheelCampaign {
+  BatchCampaign q;
+  BatchWheelOpts x;
+};
+struct BatchWheelScored {
+  BatchScoredCampaign s;
+  BatchWheelOpts x;
+};
+struct BatchWheelTrack {
+  BatchTrack t;
+  BatchWheelOpts x;
+};
+hipError_t launch_batch_finish_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelRun& w, size_t lds,
+                                      hipStream_t st);
+hipError_t launch_batch_finish_campaign_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelCampaign& w,
+                                               size_t lds, hipStream_t st);
+hipError_t launch_batch_finish_scored_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelScored& w,
+                                             size_t lds, hipStream_t st);
+hipError_t launch_batch_ingest_tracked_wheels(const BatchArgs& b, const BatchIo& io, const int* is_set,
+                                              const BatchWheelTrack& t, hipStream_t st);
 
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);

@@ -25,6 +25,7 @@
 
 #include "mppi_detmath.h"
 #include "mppi_kernels.h"
+#include "mppi_path_metrics.h"
 #include "mppi_score_chain.h"
 
 namespace mppi {

@@ -34,8 +34,10 @@ struct ScoreArgs {
   const float* v;          // [n][stride]
   const int32_t* lengths;  // [n], each in [1, stride], or null (every path has stride waypoints)
   // the log of a batch (mppi_batch_score) instead of traj / v: [n][stride][8] rows x, y, z, heading, v, w,
-  // 32-byte aligned; then lw = rw = null, lengths[p * len_step] (>= 0, clamped to stride) is path p's
-  // length, goals [n] replaces gx .. speed_on below, and rows_out [n] (or null) receives the lengths
+  // 32-byte aligned; then rw = null, lengths[p * len_step] (>= 0, clamped to stride) is path p's
+  // length, goals [n] replaces gx .. speed_on below, and rows_out [n] (or null) receives the lengths;
+  // lw is null, or the batch's wheel-contact log: rows of 6 floats (lx, ly, lz, rx, ry, rz) with the
+  // log's own row index, which the slope critic then reads in place of the body path
   const float* log;
   const ScoreGoal* goals;
   int len_step;
@@ -70,5 +72,12 @@ struct ScoreArgs {
 };
 
 hipError_t launch_score(const ScoreArgs& a, hipStream_t st);
+
+// compute_path_metrics (mppi_path_metrics.h) of the n paths of a log ([.][8] rows; lengths, len_step,
+// base_row (or null: path p begins at row p * stride) and stride as ScoreArgs has them) into out [n].
+hipError_t launch_atan2_probe(const double* y, const double* x, int64_t n, double* dm, double* dev, hipStream_t st);
+struct PathMetrics;
+hipError_t launch_log_metrics(const float* log, const int32_t* lengths, int len_step, const int64_t* base_row,
+                              int stride, int64_t n, PathMetrics* out, hipStream_t st);
 
 }  // namespace mppi

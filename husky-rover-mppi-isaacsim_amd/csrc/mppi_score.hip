@@ -30,7 +30,17 @@
 // is 12 x 32 contiguous bytes and consecutive lanes read consecutive rows.  Only x, y, z, v are
 // staged, into the same LDS rows (strides 37 and 13), so the score phase is the same code; pf_far
 // and speed_on become per-lane branches.
+//
+// LOG with WHEELS (mppi_batch_score_ex, MPPI_SLOPE_WHEELS): the batch also kept a wheel-contact log,
+// [row][6] floats (lx, ly, lz, rx, ry, rz) with the log's own row index (ScoreArgs::lw).  A thread takes
+// the 24 bytes of its waypoints' contacts beside the row and stages them into the wheel arrays' LDS rows,
+// so the slope wave is the caller-supplied paths' WHEELS code; the other three waves do not change.
+//
+// The path metrics of a log (mppi_log_metrics_kernel): compute_path_metrics of the reference in float64
+// (mppi_path_metrics.h), one lane per path: a path of L rows has (L - 2) / 20 segments of two rows each,
+// so a lane reads 64 bytes per 20 rows and the kernel is a handful of dependent loads per path.
 #include "mppi_score.h"
+#include "mppi_path_metrics.h"
 #include "mppi_score_chain.h"
 
 #include <algorithm>
@@ -101,15 +111,17 @@ __device__ __forceinline__ void stage_array(const float* __restrict__ g, float (
 // LOG: the chunk in flight, x, y, z, v of the thread's waypoints.
 constexpr int LOG_WP = TP * CT / NT;
 static_assert(LOG_WP * NT == TP * CT, "whole waypoints per thread");
-struct StageLog {
-  float q[LOG_WP][4];
+template <bool WHEELS>
+struct StageLogT {
+  float q[LOG_WP][WHEELS ? 10 : 4];  // x, y, z, v, then (WHEELS) the row's six contact floats
 };
+using StageLog = StageLogT<false>;
 
 // Waypoint u of the tile = row t0 + u % len of path p0 + u / len.  RAGGED: path p begins at row
 // base_row[p] of the log (an arena of paths of different capacities) instead of p * stride.
-template <bool STORE, bool RAGGED>
-__device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
-                                                int tid) {
+template <bool STORE, bool RAGGED, bool WHEELS>
+__device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLogT<WHEELS>& r, Smem& sm, int64_t p0, int t0,
+                                                int len, int tid) {
   const bool full = len == CT;
   const int total = TP * len;
 #pragma unroll
@@ -120,30 +132,49 @@ __device__ __forceinline__ void stage_chunk_log(const ScoreArgs& a, StageLog& r,
     const int tt = u - pp * len;
     if (p0 + pp >= a.n) continue;
     if constexpr (!STORE) {
-      const float* src;
+      size_t row;
       if constexpr (RAGGED)
-        src = a.log + ((size_t)a.base_row[p0 + pp] + (size_t)(t0 + tt)) * 8;
+        row = (size_t)a.base_row[p0 + pp] + (size_t)(t0 + tt);
       else
-        src = a.log + ((size_t)(p0 + pp) * (size_t)a.stride + (size_t)(t0 + tt)) * 8;
+        row = (size_t)(p0 + pp) * (size_t)a.stride + (size_t)(t0 + tt);
+      const float* src = a.log + row * 8;
       const float4 xyz = *reinterpret_cast<const float4*>(src);
       r.q[i][0] = xyz.x;
       r.q[i][1] = xyz.y;
       r.q[i][2] = xyz.z;
       r.q[i][3] = src[6];
+      if constexpr (WHEELS) {  // a row of the wheel log is 24 bytes: 8-byte aligned
+        const float2* w = reinterpret_cast<const float2*>(a.lw + row * 6);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float2 c = w[k];
+          r.q[i][4 + 2 * k] = c.x;
+          r.q[i][5 + 2 * k] = c.y;
+        }
+      }
     } else {
       float* dst = sm.a[0] + pp * ROW3 + 3 * tt;
       dst[0] = r.q[i][0];
       dst[1] = r.q[i][1];
       dst[2] = r.q[i][2];
       sm.v[pp * ROWV + tt] = r.q[i][3];
+      if constexpr (WHEELS) {
+        float* dl = sm.a[1] + pp * ROW3 + 3 * tt;
+        float* dr = sm.a[2] + pp * ROW3 + 3 * tt;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          dl[k] = r.q[i][4 + k];
+          dr[k] = r.q[i][7 + k];
+        }
+      }
     }
   }
 }
 
 template <int VEC, bool WHEELS, bool STORE, bool RAGGED>
-__device__ __forceinline__ void stage_chunk(const ScoreArgs& a, StageLog& r, Smem& sm, int64_t p0, int t0, int len,
-                                            int tid) {
-  stage_chunk_log<STORE, RAGGED>(a, r, sm, p0, t0, len, tid);
+__device__ __forceinline__ void stage_chunk(const ScoreArgs& a, StageLogT<WHEELS>& r, Smem& sm, int64_t p0, int t0,
+                                            int len, int tid) {
+  stage_chunk_log<STORE, RAGGED, WHEELS>(a, r, sm, p0, t0, len, tid);
 }
 
 template <int VEC, bool WHEELS, bool STORE, bool RAGGED>
@@ -165,7 +196,7 @@ using chain::slope_one;
 // RAGGED (mppi_batch_score_tasks): the LOG loader with a base row per path (ScoreArgs::base_row).
 template <int VEC, bool WHEELS, bool LOG = false, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
-  static_assert(!LOG || (VEC == 1 && !WHEELS), "the log loader takes whole rows and has no wheel arrays");
+  static_assert(!LOG || VEC == 1, "the log loader takes whole rows (WHEELS: and the rows of the wheel log)");
   static_assert(!RAGGED || LOG, "base rows belong to the log loader");
   __shared__ Smem sm;
   const int tid = threadIdx.x;
@@ -216,7 +247,7 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
     if (a.cm_path && role == 3 && p < a.n) cm = a.cm_path[p];
   }
 
-  std::conditional_t<LOG, StageLog, Stage<VEC>> r;
+  std::conditional_t<LOG, StageLogT<WHEELS>, Stage<VEC>> r;
   stage_chunk<VEC, WHEELS, false, RAGGED>(a, r, sm, p0, 0, min(CT, Lld), tid);
   stage_chunk<VEC, WHEELS, true, RAGGED>(a, r, sm, p0, 0, min(CT, Lld), tid);
   __syncthreads();
@@ -318,21 +349,70 @@ __global__ __launch_bounds__(NT) void mppi_score_kernel(ScoreArgs a) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// One lane per path of a log: the whole-path form of mppi_path_metrics.h over the path's first L rows.
+__global__ __launch_bounds__(64) void mppi_log_metrics_kernel(const float* __restrict__ log,
+                                                               const int32_t* __restrict__ lengths, int len_step,
+                                                               const int64_t* __restrict__ base_row, int stride,
+                                                               int64_t n, PathMetrics* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (p >= n) return;
+  const int L = min(max(lengths[(size_t)p * len_step], 0), stride);
+  const size_t row0 = base_row ? (size_t)base_row[p] : (size_t)p * (size_t)stride;
+  out[p] = path_metrics_rows(log + row0 * 8, 8, L);
+}
+
+// dm_atan2 (mppi_detmath.h) and the device library's atan2 on n pairs: the read-out behind
+// mppi_detmath_atan2, which lets a test compare the device's bits with the numpy restatement's and
+// measure the distance from the device's own arctangent.  One pair per lane, grid-stride.
+__global__ __launch_bounds__(256) void mppi_atan2_probe_kernel(const double* __restrict__ y, const double* __restrict__ x,
+                                                                int64_t n, double* __restrict__ dm,
+                                                                double* __restrict__ dev) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    dm[i] = dm_atan2(y[i], x[i]);
+    dev[i] = atan2(y[i], x[i]);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_atan2_probe(const double* y, const double* x, int64_t n, double* dm, double* dev, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!y || !x || !dm || !dev) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(mppi_atan2_probe_kernel, dim3(grid), dim3(256), 0, st, y, x, n, dm, dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_log_metrics(const float* log, const int32_t* lengths, int len_step, const int64_t* base_row,
+                              int stride, int64_t n, PathMetrics* out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!log || !lengths || !out || len_step < 1 || stride < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mppi_log_metrics_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, log, lengths, len_step,
+                     base_row, stride, n, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_score(const ScoreArgs& a, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
   if (a.log) {
     // stride 0: no run yet, every length is clamped to 0 and no row is read
-    if (!a.goals || !a.lengths || !a.cm || a.lw || a.rw || a.stride < 0 || a.cm_size < 1 || a.len_step < 1 ||
-        ((uintptr_t)a.log & 31) != 0 || (a.terms && !aligned16(a.terms)) ||
+    // (lw: the wheel log beside the log, rows of 24 bytes; rw stays null)
+    if (!a.goals || !a.lengths || !a.cm || a.rw || a.stride < 0 || a.cm_size < 1 || a.len_step < 1 ||
+        ((uintptr_t)a.log & 31) != 0 || ((uintptr_t)a.lw & 7) != 0 || (a.terms && !aligned16(a.terms)) ||
         (!a.base_row && a.n * (int64_t)std::max(a.stride, 1) >= ((int64_t)1 << 31)))
       return hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.n + TP - 1) / TP));
-    if (a.base_row)
+    if (a.lw) {  // the slope wave on the wheel log's two contact paths
+      if (a.base_row)
+        hipLaunchKernelGGL((mppi_score_kernel<1, true, true, true>), grid, dim3(NT), 0, st, a);
+      else
+        hipLaunchKernelGGL((mppi_score_kernel<1, true, true>), grid, dim3(NT), 0, st, a);
+    } else if (a.base_row) {
       hipLaunchKernelGGL((mppi_score_kernel<1, false, true, true>), grid, dim3(NT), 0, st, a);
-    else
+    } else {
       hipLaunchKernelGGL((mppi_score_kernel<1, false, true>), grid, dim3(NT), 0, st, a);
+    }
     return hipGetLastError();
   }
   if (!a.traj || !a.v || !a.cm || a.stride < 1 || a.cm_size < 1 || (a.lw == nullptr) != (a.rw == nullptr) ||

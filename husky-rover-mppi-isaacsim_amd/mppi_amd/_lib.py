@@ -217,6 +217,17 @@ _PROTOS = {
                                               C.POINTER(MppiBatchVariant), C.c_int32]),
     "mppi_batch_get_task_scores": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MppiPathScores),
                                              C.POINTER(C.c_int32), _DP]),
+    "mppi_batch_set_wheel_log": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mppi_batch_get_wheel_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_get_task_wheel_log": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_score_ex": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState), C.c_int32,
+                                      C.POINTER(MppiPathScores), C.POINTER(C.c_int32), _DP]),
+    "mppi_batch_score_tasks_ex": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState), C.c_int32,
+                                            C.POINTER(MppiPathScores), C.POINTER(C.c_int32), _DP]),
+    "mppi_batch_set_score_options": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mppi_batch_get_task_metrics": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP]),
+    "mppi_batch_get_run_metrics": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP]),
+    "mppi_detmath_atan2": (C.c_int, [C.c_void_p, C.c_int64, _DP, _DP, _DP, _DP]),
     "mppi_rollout_python25d": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _DP, _DP, _DP, _DP, _DP, C.c_double,
                                          C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_int32)]),
 }
@@ -781,6 +792,16 @@ class Engine:
         self._c(self.lib.mppi_get_critics(self.ctx, C.byref(k)), "mppi_get_critics")
         return critics_as_dict(k)
 
+    def detmath_atan2(self, y, x):
+        """mppi_detmath_atan2: (dm_atan2(y, x) as the device computes it, the device library's atan2(y, x)),
+        float64 arrays of y's shape (y and x broadcast)."""
+        y, x = np.broadcast_arrays(np.asarray(y, np.float64), np.asarray(x, np.float64))
+        y, x = np.ascontiguousarray(y), np.ascontiguousarray(x)
+        dm, dev = np.empty(y.shape, np.float64), np.empty(y.shape, np.float64)
+        self._c(self.lib.mppi_detmath_atan2(self.ctx, y.size, y.ctypes.data_as(_DP), x.ctypes.data_as(_DP),
+                                            dm.ctypes.data_as(_DP), dev.ctypes.data_as(_DP)), "mppi_detmath_atan2")
+        return dm, dev
+
     def score_ms(self):
         """HIP-event time (ms) of the last scoring kernel (score_paths / cost_terms)."""
         ms = C.c_double()
@@ -938,6 +959,44 @@ class Batch:
         _check(self.lib, self.lib.mppi_batch_create(engine.ctx, self.E, C.byref(h)), "mppi_batch_create")
         self.h = h
         self.tracking = None    # set_tracking's arguments while tracking is set
+        self.list_metrics = False    # the standing task list was set scored with metrics=True
+        self._opts = ("body", False)    # mppi_batch_set_score_options as last set (the library's default)
+
+    def set_wheel_log(self, on=True):
+        """mppi_batch_set_wheel_log: runs, task lists and tracking set from here on keep each log row's wheel
+        contacts (lx, ly, lz, rx, ry, rz) in an array beside the log: wheel_log() / task_wheel_log() read
+        them, score(slope="wheels") scores them.  Refused while a campaign is unfinished or tracking is set."""
+        _check(self.lib, self.lib.mppi_batch_set_wheel_log(self.h, 1 if on else 0), "mppi_batch_set_wheel_log")
+
+    def _score_options(self, slope, metrics):
+        """The options the next scored list or tracking takes; the library is told only when they change
+        (it refuses the change under tracking or an unfinished campaign: the caller ends those first)."""
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
+        want = (slope, bool(metrics))
+        if want == getattr(self, "_opts", ("body", False)):
+            return
+        _check(self.lib, self.lib.mppi_batch_set_score_options(self.h, SLOPE_MODES[slope], 1 if metrics else 0),
+               "mppi_batch_set_score_options")
+        self._opts = want
+
+    def wheel_log(self, e, first=0, count=None):
+        """Rows [count, 6] of the most recent run's wheel log: lx, ly, lz, rx, ry, rz beside log row n."""
+        if count is None:
+            count = self.episode(e)["steps_last_run"] - int(first)
+        rows = np.zeros((max(int(count), 0), 6), np.float32)
+        _check(self.lib, self.lib.mppi_batch_get_wheel_log(self.h, int(e), int(first), int(count), _fp(rows)),
+               "mppi_batch_get_wheel_log")
+        return rows
+
+    def task_wheel_log(self, i, first=0, count=None):
+        """Rows [count, 6] of task i's wheel log: lx, ly, lz, rx, ry, rz beside the task's log row n."""
+        if count is None:
+            count = self.task(i)["steps"] - int(first)
+        rows = np.zeros((max(int(count), 0), 6), np.float32)
+        _check(self.lib, self.lib.mppi_batch_get_task_wheel_log(self.h, int(i), int(first), int(count), _fp(rows)),
+               "mppi_batch_get_task_wheel_log")
+        return rows
 
     def set_episode(self, e, state: MppiState, seed, variant=-1, dem=-1, costmap=-1, trajectories=0):
         """Episode e starts at `state` with Philox key `seed` and runs with row `variant` of the table
@@ -1033,13 +1092,20 @@ class Batch:
                "mppi_batch_variant_default")
         return v
 
-    def score(self, yardstick=None, origins=None):
+    def score(self, yardstick=None, origins=None, slope="body", metrics=False):
         """mppi_batch_score: every episode's executed path (the log of its most recent run) scored on
         the device with one cost function.  yardstick: MppiBatchVariant or dict whose weights,
         collision_threshold and collision_penalty are used (default the engine's params); origins: E
         MppiState (x, y, goal_x, goal_y are read; default each episode's position when its most recent
         run began and its goal).  Returns dict(cost [E], terms [E, 4] in COST_TERMS order,
-        collisions [E], rows [E])."""
+        collisions [E], rows [E]).
+
+        slope="wheels" (mppi_batch_score_ex): the slope term over the wheel log's two contact paths, what
+        Engine.score_paths gives in the wheels mode for the log's waypoints and those contacts; needs
+        set_wheel_log() before the run.  metrics=True: also `metrics` [E, 4] float64 in
+        mppi_amd.batch.METRICS_FIELDS order (compute_path_metrics of each path)."""
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
         E = self.E
         out = dict(cost=np.zeros(E, np.float32), terms=np.zeros((E, 4), np.float32),
                    collisions=np.zeros(E, np.int32), rows=np.zeros(E, np.int32))
@@ -1052,8 +1118,15 @@ class Batch:
             if len(origins) != E:
                 raise ValueError(f"{E} episodes but {len(origins)} origins")
             o = (MppiState * E)(*origins)
-        _check(self.lib, self.lib.mppi_batch_score(self.h, y, o, C.byref(sc), out["rows"].ctypes.data_as(i32)),
-               "mppi_batch_score")
+        if slope == "body" and not metrics:
+            _check(self.lib, self.lib.mppi_batch_score(self.h, y, o, C.byref(sc), out["rows"].ctypes.data_as(i32)),
+                   "mppi_batch_score")
+            return out
+        if metrics:
+            out["metrics"] = np.zeros((E, 4), np.float64)
+        _check(self.lib, self.lib.mppi_batch_score_ex(
+            self.h, y, o, SLOPE_MODES[slope], C.byref(sc), out["rows"].ctypes.data_as(i32),
+            out["metrics"].ctypes.data_as(_DP) if metrics else None), "mppi_batch_score_ex")
         return out
 
     def run(self, n_steps, proj="3d", policy=None):
@@ -1075,14 +1148,22 @@ class Batch:
             raise ValueError(f"{name} is on device {index}, the engine's is {self.engine.device}")
         return ptr
 
-    def set_tracking(self, yardstick=None, max_steps=None, runs_per_episode=1, keep_log=True, goal_tol=0.5):
+    def set_tracking(self, yardstick=None, max_steps=None, runs_per_episode=1, keep_log=True, goal_tol=0.5,
+                     slope="body", metrics=False):
         """mppi_batch_set_tracking: from here on step_device tracks a run per set episode on the device:
         it logs each ingested state beside the command before it, tests the goal (goal_tol) and the
         step cap max_steps, scores the run with `yardstick` (MppiBatchVariant or dict whose weights,
         collision_threshold and collision_penalty are used; default the engine's params) and writes
         its result into one of the episode's runs_per_episode result rows; an ended episode idles
         until its next reset.  keep_log=False: no log row is written (log() then has no rows).
-        Setting it again starts every run and count over.  runs() / run_counts() read the results."""
+        Setting it again starts every run and count over.  runs() / run_counts() read the results.
+
+        slope="wheels": the run's slope term is the wheel form, over the contacts the ingest forms from each
+        ingested pose and the episode's DEM; metrics=True: runs() also returns `metrics` [R, 4] float64
+        (mppi_amd.batch.path_metrics of the run's rows).  With set_wheel_log() on and keep_log the contacts
+        are kept too (wheel_log())."""
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
         if max_steps is None:
             raise ValueError("set_tracking needs max_steps, the step cap of a run (clear_tracking() turns tracking off)")
         max_steps, runs_per_episode = int(max_steps), int(runs_per_episode)
@@ -1093,9 +1174,14 @@ class Batch:
         if not float(goal_tol) >= 0:
             raise ValueError(f"goal_tol must be >= 0, got {goal_tol!r}")
         y = None if yardstick is None else C.byref(_as_variant(yardstick))
+        if getattr(self, "tracking", None) and (slope, bool(metrics)) != getattr(self, "_opts", ("body", False)):
+            self.clear_tracking()    # (the library refuses new options under tracking; setting it again starts over anyway)
+        self._score_options(slope, metrics)
         _check(self.lib, self.lib.mppi_batch_set_tracking(self.h, y, float(goal_tol), max_steps, runs_per_episode,
                                                           1 if keep_log else 0), "mppi_batch_set_tracking")
         self.tracking = dict(max_steps=max_steps, runs_per_episode=runs_per_episode, keep_log=bool(keep_log))
+        if slope != "body" or metrics:
+            self.tracking.update(slope=slope, metrics=bool(metrics))
 
     def clear_tracking(self):
         """Turn tracking off and free its tables: step_device is the plain device step again."""
@@ -1116,7 +1202,8 @@ class Batch:
         """mppi_batch_get_runs: the result rows of tracked runs.  e: an episode -> dict of arrays over its
         runs_per_episode rows: run (the ordinal), state [R, 11] (mppi_state order, at the ending
         ingest), steps, reached, status (0: no run has ended into the row, 1: reached, 2: the cap,
-        3: abandoned), cost, terms [R, 4], collisions, rows, length (float64).  e=None: every
+        3: abandoned), cost, terms [R, 4], collisions, rows, length (float64), and metrics [R, 4] (float64,
+        mppi_amd.batch.METRICS_FIELDS) when tracking was set with metrics=True.  e=None: every
         episode's rows stacked, with an `episode` column (mppi_amd.batch.campaign_summary takes it)."""
         tr = getattr(self, "tracking", None)
         if not tr:
@@ -1141,6 +1228,10 @@ class Batch:
             out["status"].ctypes.data_as(i32), C.byref(sc), out["rows"].ctypes.data_as(i32),
             out["length"].ctypes.data_as(_DP)), "mppi_batch_get_runs")
         out["state"] = np.frombuffer(bytes(st), dtype=np.float32).reshape(R, 11).copy()
+        if tr.get("metrics"):
+            out["metrics"] = np.zeros((R, 4), np.float64)
+            _check(self.lib, self.lib.mppi_batch_get_run_metrics(self.h, e, 0, R, out["metrics"].ctypes.data_as(_DP)),
+                   "mppi_batch_get_run_metrics")
         return out
 
     def step_device(self, states, mask=None, reset=None, seeds=None, cmd=None, plan=None, proj="3d", z=None,
@@ -1222,7 +1313,7 @@ class Batch:
         return rows
 
     # ---- the task queue: N tasks on the E episodes as lanes (mppi_batch_set_tasks / _run_tasks) ----
-    def set_tasks(self, tasks, scored=None, keep_log=True):
+    def set_tasks(self, tasks, scored=None, keep_log=True, slope="body", metrics=False):
         """The batch's task list: MppiBatchTask (make_task) or dicts of make_task's arguments; an empty
         list clears it.  The results are reset.
 
@@ -1230,9 +1321,37 @@ class Batch:
         (mppi_batch_set_tasks_scored): True for the engine's params, or a MppiBatchVariant / dict whose
         weights, collision_threshold and collision_penalty are used; task_scores() then reads the
         scores.  keep_log=False (scored lists only): no log arena is allocated, so task_log and
-        score_tasks raise and the sum of the step caps has no limit."""
+        score_tasks raise and the sum of the step caps has no limit.
+
+        slope="wheels" (scored lists): the slope term of the online score in its wheel form (the contacts
+        of every executed step; no log needed); metrics=True (scored lists): a `metrics` row per task
+        (compute_path_metrics; task_scores() returns it).  Both are refused for a plain list, which scores
+        nothing as it runs.  scored=dict(yardstick=None | variant, slope=, metrics=) says the same in one
+        argument: a dict with the key `yardstick`, `slope` or `metrics` holds exactly those keys (a
+        yardstick's own fields go under `yardstick`), and then the two keywords must be left alone."""
+        if isinstance(scored, dict) and (set(scored) & {"slope", "metrics", "yardstick"}):
+            # the one-argument form: exactly these keys, never mixed with a yardstick's fields
+            extra = set(scored) - {"slope", "metrics", "yardstick"}
+            if extra:
+                raise ValueError(f"scored=dict(yardstick=, slope=, metrics=) takes no other key, got {sorted(extra)}: "
+                                 "a yardstick's fields go under `yardstick`")
+            if slope != "body" or metrics:
+                raise ValueError("give slope / metrics either as keywords or inside scored=dict(...), not both")
+            slope, metrics = scored.get("slope", "body"), scored.get("metrics", False)
+            scored = True if scored.get("yardstick") is None else scored["yardstick"]
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
+        if (slope != "body" or metrics) and (scored is None or scored is False):
+            raise ValueError("slope / metrics belong to a scored list (scored=True or a yardstick): a plain list "
+                             "scores nothing as it runs (score_tasks(slope=, metrics=) scores its log afterwards)")
+        opts = dict(slope=slope, metrics=bool(metrics))
         rows = [t if isinstance(t, MppiBatchTask) else make_task(**dict(t)) for t in tasks]
         arr = (MppiBatchTask * max(len(rows), 1))(*rows)
+        if (opts["slope"], opts["metrics"]) != getattr(self, "_opts", ("body", False)) and scored is not None and scored is not False:
+            # (the library refuses new options while a campaign is unfinished: the old list goes first)
+            _check(self.lib, self.lib.mppi_batch_set_tasks(self.h, 0, arr), "mppi_batch_set_tasks")
+            self._score_options(opts["slope"], opts["metrics"])
+        self.list_metrics = False
         if scored is None or scored is False:
             if not keep_log:
                 raise ValueError("keep_log=False needs a scored list (scored=True or a yardstick): "
@@ -1242,6 +1361,7 @@ class Batch:
             y = None if scored is True else C.byref(_as_variant(scored))
             _check(self.lib, self.lib.mppi_batch_set_tasks_scored(self.h, len(rows), arr, y, 1 if keep_log else 0),
                    "mppi_batch_set_tasks_scored")
+            self.list_metrics = getattr(self, "_opts", ("body", False))[1] and len(rows) > 0
         self.n_tasks = len(rows)
 
     def task_scores(self, first=0, count=None):
@@ -1262,6 +1382,10 @@ class Batch:
                                                              out["rows"].ctypes.data_as(i32),
                                                              out["length"].ctypes.data_as(_DP)),
                "mppi_batch_get_task_scores")
+        if getattr(self, "list_metrics", False):
+            out["metrics"] = np.zeros((n, 4), np.float64)
+            _check(self.lib, self.lib.mppi_batch_get_task_metrics(self.h, first, n, out["metrics"].ctypes.data_as(_DP)),
+                   "mppi_batch_get_task_metrics")
         return out
 
     def run_tasks(self, n_steps, proj="3d", policy=None):
@@ -1290,10 +1414,12 @@ class Batch:
                "mppi_batch_get_task_log")
         return rows
 
-    def score_tasks(self, yardstick=None, origins=None):
+    def score_tasks(self, yardstick=None, origins=None, slope="body", metrics=False):
         """mppi_batch_score_tasks: score() over the N task logs, each on its task's costmap; origins: N
         MppiState (default each task's start and goal).  Returns dict(cost [N], terms [N, 4],
-        collisions [N], rows [N])."""
+        collisions [N], rows [N]); slope, metrics: as score() (mppi_batch_score_tasks_ex)."""
+        if slope not in SLOPE_MODES:
+            raise ValueError(f"slope must be one of {sorted(SLOPE_MODES)}, got {slope!r}")
         N = int(getattr(self, "n_tasks", 0))
         out = dict(cost=np.zeros(N, np.float32), terms=np.zeros((N, 4), np.float32),
                    collisions=np.zeros(N, np.int32), rows=np.zeros(N, np.int32))
@@ -1306,8 +1432,16 @@ class Batch:
             if len(origins) != N:
                 raise ValueError(f"{N} tasks but {len(origins)} origins")
             o = (MppiState * max(N, 1))(*origins)
-        _check(self.lib, self.lib.mppi_batch_score_tasks(self.h, y, o, C.byref(sc), out["rows"].ctypes.data_as(i32)),
-               "mppi_batch_score_tasks")
+        if slope == "body" and not metrics:
+            _check(self.lib, self.lib.mppi_batch_score_tasks(self.h, y, o, C.byref(sc),
+                                                             out["rows"].ctypes.data_as(i32)),
+                   "mppi_batch_score_tasks")
+            return out
+        if metrics:
+            out["metrics"] = np.zeros((N, 4), np.float64)
+        _check(self.lib, self.lib.mppi_batch_score_tasks_ex(
+            self.h, y, o, SLOPE_MODES[slope], C.byref(sc), out["rows"].ctypes.data_as(i32),
+            out["metrics"].ctypes.data_as(_DP) if metrics else None), "mppi_batch_score_tasks_ex")
         return out
 
     def last_ms(self):

@@ -217,6 +217,74 @@ def path_length(rows):
     return length
 
 
+def dm_atan2(y, x):
+    """The deterministic float64 arctangent of csrc/mppi_detmath.h (dm_atan2), the same IEEE operations in
+    the same order, so a device result equals this bit for bit.  Arrays or scalars (broadcast), finite.
+
+    t = min(|y|, |x|) / max(|y|, |x|) (0 for y = x = 0); three half-angle steps t <- t / (1 + sqrt(1 + t t));
+    the 12-term odd series in Horner form over z = t t, times t, times 8; |y| > |x|: pi/2 - r; x < 0:
+    pi - r; y < 0: -r.  A signed zero counts as +0."""
+    y = np.asarray(y, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    y, x = np.broadcast_arrays(y, x)
+    ay = np.where(y < 0.0, -y, y)
+    ax = np.where(x < 0.0, -x, x)
+    small = ay < ax
+    mn = np.where(small, ay, ax)
+    mx = np.where(small, ax, ay)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(mx > 0.0, mn / np.where(mx > 0.0, mx, 1.0), 0.0)
+    for _ in range(3):
+        t = t / (1.0 + np.sqrt(1.0 + t * t))
+    z = t * t
+    p = np.full(z.shape, -1.0 / 23.0)
+    for c in (1.0 / 21.0, -1.0 / 19.0, 1.0 / 17.0, -1.0 / 15.0, 1.0 / 13.0, -1.0 / 11.0, 1.0 / 9.0, -1.0 / 7.0,
+              1.0 / 5.0, -1.0 / 3.0, 1.0):
+        p = p * z + c
+    r = (t * p) * 8.0
+    r = np.where(ay > ax, 1.5707963267948966 - r, r)
+    r = np.where(x < 0.0, 3.141592653589793 - r, r)
+    r = np.where(y < 0.0, -r, r)
+    return r if r.ndim else np.float64(r)
+
+
+METRICS_STRIDE = 20                  # compute_path_metrics' k (MPPI_isaac.py:236)
+METRICS_FIELDS = ("length20", "angle_up", "angle_down", "distance_up")     # mppi_path_metrics
+DEGREES = 57.29577951308232          # 180 / pi, np.degrees' factor
+
+
+def path_metrics(rows):
+    """compute_path_metrics of MPPI_isaac.py:231-256 (k = 20) on logged waypoints, in float64: the
+    `metrics` of a scored task list, a tracked run or Batch.score(metrics=True), bit for bit
+    (csrc/mppi_path_metrics.h is the device's statement).  rows: [L, >= 3] float32, x, y, z first.
+
+    Segments m = 0, 1, ... while 20 m + 21 < L: s = p[20 m + 21] - p[20 m], the float32 coordinates
+    widened first (the reference's p[i + 20] - p[i - 1] over i = 1, 21, ... < L - 20; neighbours overlap
+    by one row).  hh = s.x s.x + s.y s.y, n = sqrt(hh + s.z s.z); length20 += n; if n > 0:
+    a = dm_atan2(s.z, sqrt(hh)) (180 / pi), added to angle_up if a > 0, else |a| to angle_down; if
+    s.z > 0: distance_up += s.z.  Sums in row order.  Returns float64 [4] in METRICS_FIELDS order;
+    fewer than 22 rows give zeros."""
+    rows = np.asarray(rows, dtype=F32)
+    L = len(rows)
+    p = rows.reshape(L, rows.shape[-1] if rows.ndim > 1 else 3)[:, :3].astype(np.float64)
+    length = up = down = climbed = np.float64(0.0)
+    k = METRICS_STRIDE
+    for i in range(0, L - k - 1, k):
+        s = p[i + k + 1] - p[i]
+        hh = s[0] * s[0] + s[1] * s[1]
+        n = np.sqrt(hh + s[2] * s[2])
+        length = length + n
+        if n > 0.0:
+            a = dm_atan2(s[2], np.sqrt(hh)) * DEGREES
+            if a > 0.0:
+                up = up + a
+            else:
+                down = down + np.abs(a)
+        if s[2] > 0.0:
+            climbed = climbed + s[2]
+    return np.array([length, up, down, climbed], dtype=np.float64)
+
+
 SUMMARY_FIELDS = ("cost", "path", "slope", "speed", "obstacle", "length")
 
 
@@ -235,7 +303,9 @@ def campaign_summary(results, by=None):
 
     Returns {key: dict(count, reached, collided (runs with at least one collision), mean=dict(cost,
     path, slope, speed, obstacle, length), std=the same fields)} in float64, the standard deviation
-    the population's (numpy's default), keys in order of first appearance."""
+    the population's (numpy's default), keys in order of first appearance.  When every result carries
+    `metrics` (4 values in METRICS_FIELDS order: the runs were scored with metrics=True), mean and std
+    also hold length20, angle_up, angle_down and distance_up."""
     if isinstance(results, dict):
         results, by = tracked_results(results, by)
     results = list(results)
@@ -250,10 +320,15 @@ def campaign_summary(results, by=None):
         terms = np.asarray([np.asarray(r["terms"], np.float64).reshape(4) for r in rs])
         cols = dict(cost=np.asarray([r["cost"] for r in rs], np.float64), path=terms[:, 0], slope=terms[:, 1],
                     speed=terms[:, 2], obstacle=terms[:, 3], length=np.asarray([r["length"] for r in rs], np.float64))
+        fields = SUMMARY_FIELDS
+        if all(r.get("metrics") is not None for r in rs):
+            met = np.asarray([np.asarray(r["metrics"], np.float64).reshape(4) for r in rs])
+            cols.update({f: met[:, j] for j, f in enumerate(METRICS_FIELDS)})
+            fields = SUMMARY_FIELDS + METRICS_FIELDS
         out[k] = dict(count=len(rs), reached=sum(1 for r in rs if r["reached"]),
                       collided=sum(1 for r in rs if int(r["collisions"]) > 0),
-                      mean={f: float(np.mean(cols[f])) for f in SUMMARY_FIELDS},
-                      std={f: float(np.std(cols[f])) for f in SUMMARY_FIELDS})
+                      mean={f: float(np.mean(cols[f])) for f in fields},
+                      std={f: float(np.std(cols[f])) for f in fields})
     return out
 
 
@@ -274,7 +349,8 @@ def tracked_results(runs, by=None, abandoned=False):
     keep = [i for i in range(len(ep)) if status[i] in ((1, 2, 3) if abandoned else (1, 2))]
     out = [dict(episode=int(ep[i]), run=int(runs["run"][i]), status=int(status[i]), reached=bool(runs["reached"][i]),
                 loops=int(runs["steps"][i]), cost=runs["cost"][i], terms=runs["terms"][i],
-                collisions=runs["collisions"][i], length=runs["length"][i]) for i in keep]
+                collisions=runs["collisions"][i], length=runs["length"][i],
+                **({"metrics": runs["metrics"][i]} if "metrics" in runs else {})) for i in keep]
     return out, [None if by is None else by[int(ep[i])] for i in keep]
 
 
@@ -282,7 +358,8 @@ def campaign_results(tasks, scores):
     """run_campaign's (per-task dicts, score arrays) as the per-task dicts campaign_summary takes:
     each task's dict with its cost, terms, collisions and length added."""
     return [dict(t, cost=scores["cost"][i], terms=scores["terms"][i], collisions=scores["collisions"][i],
-                 length=scores["length"][i]) for i, t in enumerate(tasks)]
+                 length=scores["length"][i], **({"metrics": scores["metrics"][i]} if "metrics" in scores else {}))
+            for i, t in enumerate(tasks)]
 
 
 def normalise_heading(hv):

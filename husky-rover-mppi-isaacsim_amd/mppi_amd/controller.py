@@ -561,7 +561,7 @@ class MPPI_Controller:
         return batch
 
     def batch_stepper(self, episodes, seeds=None, variants=None, episode_variant=None, dems=None, costmaps=None,
-                      episode_dem=None, episode_costmap=None, episode_trajectories=None, track=None):
+                      episode_dem=None, episode_costmap=None, episode_trajectories=None, track=None, wheel_log=False):
         """E controllers for E rovers of an external, vectorised simulator (mppi_batch_step_device,
         DESIGN.md §3.7): the Isaac loop (visual_terrain_stack_full_terrain.py:466-515) with the poses
         kept in device tensors.  episodes: the E initial states (state dicts of mppi_amd.batch, or
@@ -574,15 +574,22 @@ class MPPI_Controller:
         every step, so read them in stream order), .batch (the _lib.Batch) and .close().
 
         track: None, or the arguments of _lib.Batch.set_tracking as a dict (max_steps, and optionally
-        yardstick, runs_per_episode, keep_log, goal_tol): a tracked stepper, whose runs are logged, tested
-        against goal and step cap, scored and ended on the device.  .step then takes z= and done= and
-        returns (cmd, plan, done); .runs() reads the results once the campaign is over.
+        yardstick, runs_per_episode, keep_log, goal_tol, slope, metrics): a tracked stepper, whose runs are
+        logged, tested against goal and step cap, scored and ended on the device.  .step then takes z= and
+        done= and returns (cmd, plan, done); .runs() reads the results once the campaign is over.
+        slope="wheels" scores the slope term over the wheel contacts the ingest forms from each pose,
+        metrics=True adds compute_path_metrics per run; wheel_log=True keeps the contacts beside the log
+        (.batch.wheel_log(e)); it needs `track` with keep_log, and is refused without `track`.
         """
+        if wheel_log and track is None:
+            raise ValueError("wheel_log=True needs track=...: the plain device step keeps no log")
         states = [s if isinstance(s, _lib.MppiState) else to_mppi_state(s) for s in episodes]
         batch = self._open_batch(len(states), lambda: states, seeds, variants, episode_variant, dems, costmaps, episode_dem,
                                  episode_costmap, episode_trajectories)
         if track is not None:
             try:
+                if wheel_log:
+                    batch.set_wheel_log()
                 batch.set_tracking(**dict(track))
             except Exception:
                 batch.close()
@@ -591,7 +598,7 @@ class MPPI_Controller:
 
     def run_batch(self, starts, headings, goals, seeds=None, proj="3d", max_loops=None, policy=None,
                   variants=None, episode_variant=None, score=None, dems=None, costmaps=None, episode_dem=None,
-                  episode_costmap=None, episode_trajectories=None):
+                  episode_costmap=None, episode_trajectories=None, slope="body", metrics=False, wheel_log=False):
         """run() for many episodes at once on this controller's surface and parameters (mppi_batch_*,
         DESIGN.md §3.7): episode e starts at starts[e] = (x, y) with heading headings[e] (normalised
         as Robot does), wheels at rest and the controller's std_dev_u1 / std_dev_u2, and drives to
@@ -622,7 +629,17 @@ class MPPI_Controller:
         Returns one dict per episode: x, y, z, lin_vel, ang_vel (the lists Robot accumulates: x, y, z
         begin with the start pose and z = 0), loops, reached; with `score` the pair (that list,
         dict(cost [E], terms [E, 4], collisions [E], rows [E])).
+
+        slope="wheels" (with `score`): the slope term is the controller's own wheel form, over the wheel
+        contacts of every executed step (they exist under both projections, so one wheel yardstick serves
+        a 2D-vs-3D comparison); metrics=True: the scores also hold `metrics` [E, 4], compute_path_metrics
+        of every path (mppi_amd.batch.METRICS_FIELDS).  wheel_log=True (implied by slope="wheels", which
+        scores the kept contacts after the run): every episode's dict also holds `wheels` [loops, 6], the
+        contacts lx, ly, lz, rx, ry, rz of each step.  slope / metrics without `score` are refused.
         """
+        if (slope != "body" or metrics) and (score is None or score is False):
+            raise ValueError("slope / metrics belong to `score`: give score=True or a yardstick")
+        wheel_log = bool(wheel_log) or slope == "wheels"
         starts = np.asarray(starts, np.float64).reshape(-1, 2)
         E = starts.shape[0]
         headings = np.asarray(headings, np.float64).reshape(E, 3)
@@ -633,6 +650,8 @@ class MPPI_Controller:
                                         self.std_dev_u1, self.std_dev_u2) for e in range(E)],
             seeds, variants, episode_variant, dems, costmaps, episode_dem, episode_costmap, episode_trajectories)
         try:
+            if wheel_log:
+                batch.set_wheel_log()
             batch.run(self.max_loops if max_loops is None else int(max_loops), proj, pol)
             out = []
             for e in range(E):
@@ -641,15 +660,18 @@ class MPPI_Controller:
                 out.append(dict(x=[starts[e, 0]] + list(rows[:, 0]), y=[starts[e, 1]] + list(rows[:, 1]),
                                 z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
                                 loops=info["steps_last_run"], reached=info["reached"]))
+                if wheel_log:
+                    out[-1]["wheels"] = batch.wheel_log(e, 0, info["steps_last_run"])
             if score is None or score is False:
                 return out
-            return out, batch.score(None if score is True else score)
+            return out, batch.score(None if score is True else score, slope=slope, metrics=metrics)
         finally:
             batch.close()
 
     def run_campaign(self, starts, headings, goals, seeds=None, lanes=64, max_loops=None, proj="3d", policy=None,
                      variants=None, task_variant=None, score=None, dems=None, costmaps=None, task_dem=None,
-                     task_costmap=None, task_trajectories=None, log=True):
+                     task_costmap=None, task_trajectories=None, log=True, slope="body", metrics=False,
+                     wheel_log=False):
         """run_batch for N tasks on `lanes` episodes (mppi_batch_set_tasks / _run_tasks):
         the lane whose task ends (goal reached, or its step cap) takes the next task of the list on the
         GPU in the same step, so a campaign of runs of very different lengths keeps every lane busy
@@ -667,10 +689,18 @@ class MPPI_Controller:
         size is not bounded by the sum of its step caps; the per-task dicts then hold `loops`,
         `reached` and the final `x`, `y` only.
 
+        slope="wheels" / metrics=True (with `score`): the online score's slope term in the wheel form, and
+        `metrics` [N, 4] beside the scores (campaign_summary then reports their per-variant means); both
+        work with log=False, and slope="wheels" does not turn the wheel log on here: the lanes extend the
+        chain by the contacts as they run.  wheel_log=True (needs log): each task's dict also holds `wheels`
+        [loops, 6].  slope / metrics without `score` are refused.
+
         Returns what run_batch returns, one dict per task (with `score` the pair; mppi_amd.batch
         campaign_results / campaign_summary turn the pair into the per-variant table).
         """
         scored = not (score is None or score is False)
+        if (slope != "body" or metrics) and not scored:
+            raise ValueError("slope / metrics belong to `score`: give score=True or a yardstick")
         if not log and not scored:
             raise ValueError("log=False needs score=True or a yardstick: without a log nothing else is kept of a run")
         starts = np.asarray(starts, np.float64).reshape(-1, 2)
@@ -696,11 +726,15 @@ class MPPI_Controller:
                 self._fill_dem_slot(batch, slot, Z)
             for slot, cm in enumerate(costmaps or []):
                 self._fill_costmap_slot(batch, slot, cm)
+            if wheel_log:
+                if not log:
+                    raise ValueError("wheel_log=True needs log=True: the contacts are kept beside the log rows")
+                batch.set_wheel_log()
             batch.set_tasks([_lib.make_task(_lib.make_state(starts[i, 0], starts[i, 1], headings[i], 0.0, 0.0,
                                                             goals[i, 0], goals[i, 1], self.std_dev_u1,
                                                             self.std_dev_u2),
                                             seeds[i], caps[i], tv[i], td[i], tc[i], tk[i]) for i in range(N)],
-                            scored=score if scored else None, keep_log=bool(log))
+                            scored=score if scored else None, keep_log=bool(log), slope=slope, metrics=bool(metrics))
             done = 0
             while done < N:     # every task ends within its cap, so the campaign ends
                 done, _ = batch.run_tasks(max(caps), proj, pol)
@@ -715,6 +749,8 @@ class MPPI_Controller:
                 out.append(dict(x=[starts[i, 0]] + list(rows[:, 0]), y=[starts[i, 1]] + list(rows[:, 1]),
                                 z=[0] + list(rows[:, 2]), lin_vel=list(rows[:, 6]), ang_vel=list(rows[:, 7]),
                                 loops=info["steps"], reached=info["reached"]))
+                if wheel_log:
+                    out[-1]["wheels"] = batch.task_wheel_log(i, 0, info["steps"])
             if not scored:
                 return out
             return out, batch.task_scores()

@@ -864,6 +864,69 @@ int mppi_rollout_python25d(mppi_ctx* ctx, int64_t n, int32_t H, const double* x0
  * any bit (0 expected). */
 int mppi_selftest(mppi_ctx* ctx, int32_t what, int64_t n, uint64_t seed, int64_t* mismatches);
 
+/* ---- Executed paths: wheel contacts, the wheel form of the slope critic, path metrics ----
+ *
+ * A log row holds x, y, z, heading, v, w.  The three options below add what the controller itself
+ * steers by and what the 2D-vs-3D comparison quotes per run.  All are opt-in: a batch that calls none
+ * of these entry points allocates, launches and computes what it did without them.
+ *
+ * The wheel log.  mppi_batch_set_wheel_log(b, 1): runs (mppi_batch_run), task lists (mppi_batch_set_tasks,
+ * _set_tasks_scored with keep_log) and tracking (mppi_batch_set_tracking with keep_log) that are set
+ * afterwards keep, beside every log row, the row's wheel contacts lx, ly, lz, rx, ry, rz: 24 bytes per
+ * row in an array parallel to the log; the 8-float log row and its getters do not change.  Own model:
+ * row n's contacts are row 0 of left_wheel_sim / right_wheel_sim of that step's optimal rollout (floats
+ * 4H + 6 .. 4H + 11 of the plan), the bits of the single-context mppi_step, whichever projection planned.
+ * Tracked steps: the ingest forms them from the ingested pose by the rollout's rule
+ * (projection_warp.py:331-347): q = the corners of the cell of (x, y) on the episode's DEM,
+ * n = normal_on_grid(q), c = cross(n, heading as given), r = wheel_offset (c.x, c.y), left =
+ * (x + r.x, y + r.y, Z[cell(x + r.x, y + r.y)]), right the same with -r; IEEE float32 / and sqrt.
+ * MPPI_ESTATE while a campaign is unfinished or tracking is set.  The getters mirror mppi_batch_get_log
+ * and mppi_batch_get_task_log (rows6: count * 6 floats); MPPI_ESTATE when the log has no wheel log. */
+int mppi_batch_set_wheel_log(mppi_batch* b, int32_t enable);
+int mppi_batch_get_wheel_log(mppi_batch* b, int32_t e, int32_t first, int32_t count, float* rows6);
+int mppi_batch_get_task_wheel_log(mppi_batch* b, int32_t i, int32_t first, int32_t count, float* rows6);
+
+/* compute_path_metrics of the reference (MPPI_isaac.py:231-256, k = 20) of one executed path, float64.
+ * Waypoints: the rows' float32 (x, y, z) widened.  Segments m = 0, 1, ... while 20 m + 21 < rows:
+ * s = p[20 m + 21] - p[20 m]; hh = s.x s.x + s.y s.y; n = sqrt(hh + s.z s.z); length20 += n; if n > 0:
+ * a = dm_atan2(s.z, sqrt(hh)) (180 / pi), a > 0 adds a to angle_up, else |a| to angle_down; if s.z > 0:
+ * distance_up += s.z.  Sums in row order, no fused operation; fewer than 22 rows give zeros.  dm_atan2 is
+ * the deterministic arctangent of csrc/mppi_detmath.h; mppi_amd.batch.path_metrics is the numpy form. */
+typedef struct mppi_path_metrics {
+  double length20, angle_up, angle_down, distance_up;
+} mppi_path_metrics;
+
+/* mppi_batch_score / mppi_batch_score_tasks with a choice of the slope term and the path metrics.
+ * slope_mode MPPI_SLOPE_BODY: the existing entry points' results.  MPPI_SLOPE_WHEELS: the slope term
+ * reads the wheel log's two contact paths: cost, terms, collisions and rows are bitwise those of
+ * mppi_score_paths on a context in MPPI_SLOPE_WHEELS given the log's (x, y, z) as traj, the wheel log's
+ * halves as left_wheel / right_wheel, the log's v and the same origin, yardstick and costmap;
+ * MPPI_ESTATE, naming mppi_batch_set_wheel_log, when the log has no wheel log.  metrics: [E] ([N] for
+ * tasks) rows or NULL. */
+int mppi_batch_score_ex(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                        int32_t slope_mode, mppi_path_scores* out, int32_t* rows, mppi_path_metrics* metrics);
+int mppi_batch_score_tasks_ex(mppi_batch* b, const mppi_batch_variant* yardstick, const mppi_state* origins,
+                              int32_t slope_mode, mppi_path_scores* out, int32_t* rows,
+                              mppi_path_metrics* metrics);
+
+/* The same for the scores computed as the run goes: the next mppi_batch_set_tasks_scored or
+ * mppi_batch_set_tracking takes slope_mode and metrics with its yardstick (default MPPI_SLOPE_BODY, 0).
+ * In MPPI_SLOPE_WHEELS the advance lane (own model) or the ingest (tracked steps) extends the slope
+ * chain over the row's wheel contacts; the score rows are bitwise mppi_batch_score_tasks_ex / _score_ex
+ * on the same rows, with or without a log.  metrics != 0: a mppi_path_metrics row beside every score
+ * row (zeros until the task or run ends).  MPPI_ESTATE while a campaign is unfinished or tracking is
+ * set; the getters answer MPPI_ESTATE when the list or tracking was set without the metrics. */
+int mppi_batch_set_score_options(mppi_batch* b, int32_t slope_mode, int32_t metrics);
+int mppi_batch_get_task_metrics(mppi_batch* b, int32_t first, int32_t count, mppi_path_metrics* metrics);
+int mppi_batch_get_run_metrics(mppi_batch* b, int32_t e, int32_t first, int32_t count,
+                               mppi_path_metrics* metrics);
+
+/* A read-out of the deterministic float64 arctangent on the device, for tests and measurements: for
+ * the n pairs y[i], x[i] (host arrays, n <= 2^28) dm[i] = dm_atan2(y[i], x[i]) as the metrics' kernels
+ * compute it (bitwise mppi_amd.batch.dm_atan2) and dev[i] = the device library's own atan2.  One small
+ * kernel on the context's stream; synchronous; changes no state of the context. */
+int mppi_detmath_atan2(mppi_ctx* ctx, int64_t n, const double* y, const double* x, double* dm, double* dev);
+
 #ifdef __cplusplus
 }
 #endif

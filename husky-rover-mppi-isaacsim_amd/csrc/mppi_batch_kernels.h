@@ -47,6 +47,33 @@ __global__ __launch_bounds__(256) void mppi_batch_noise_kernel(const BatchArgs b
   noise_waves(ep->seed, ep->step * (uint64_t)NB, k_offset, H, (int)blockIdx.x * 4 + wave, blocks * NB * 4,
               (int)gridDim.x * 4, eps, (int)threadIdx.x & 63);
 }
+// The same under sampling plans (mppi_set_sampling / mppi_batch_set_variant_sampling): the episode's
+// plan is the row behind its variant where the caller gave one (antithetic >= 0), else the context's,
+// all wave-uniform.  beta > 0 takes the serial form over the episode's (leaf block, 64 trajectories)
+// wave-units, the elementwise plans the units above, the default plan the generator above.
+__global__ __launch_bounds__(256) void mppi_batch_noise_plan_kernel(const BatchArgs b, int64_t k_offset,
+                                                                    const BatchNoisePlan np) {
+  const int e = blockIdx.y;
+  const BatchEpisode* ep = b.ep + e;
+  if (!ep->active) return;
+  SamplePlan pl = np.ctx;
+  if (np.rows) {
+    const int vi = b.ep_var[e];
+    if (vi >= 0 && np.rows[vi].antithetic >= 0) pl = np.rows[vi];
+  }
+  const int H = b.H, NB = (H + 1) >> 1;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  float* eps = b.eps + (size_t)e * b.blocks * 2 * H * 256;
+  const int blocks = b.scene ? b.scene->rec[e].blocks : b.blocks;
+  const int q0 = (int)blockIdx.x * 4 + wave, stride = (int)gridDim.x * 4, lane = (int)threadIdx.x & 63;
+  if (pl.beta > 0.0f)
+    noise_serial(ep->seed, ep->step * (uint64_t)NB, k_offset, H, q0, blocks * 4, stride, eps, lane, pl);
+  else if (pl.antithetic | pl.nominal)
+    noise_waves<true>(ep->seed, ep->step * (uint64_t)NB, k_offset, H, q0, blocks * NB * 4, stride, eps, lane,
+                      pl.antithetic, pl.nominal);
+  else
+    noise_waves(ep->seed, ep->step * (uint64_t)NB, k_offset, H, q0, blocks * NB * 4, stride, eps, lane);
+}
 
 // The role-split rollout of leaf block blockIdx.x of episode blockIdx.y: the launch's RolloutArgs
 // (scene and parameters) with the episode's state, derived critic fields, seed, Philox base and
@@ -948,11 +975,14 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
   tracked_ingest<true>(b, io, is_set, w.t, &w.x);
 }
 
-hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st) {
+hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st, const BatchNoisePlan& np) {
   // about four wave-units (two noise_waves iterations) per wave
   const int units = b.blocks * ((b.H + 1) >> 1) * 4;
   const unsigned g = (unsigned)std::min(std::max((units + 15) / 16, 1), 64);
-  hipLaunchKernelGGL(mppi_batch_noise_kernel, dim3(g, (unsigned)b.E), dim3(256), 0, st, b, k_offset);
+  // (no plan row and the default plan on the context: the kernel as it was before there were plans)
+  const bool plain = !np.rows && !np.ctx.antithetic && !np.ctx.nominal && !(np.ctx.beta > 0.0f);
+  if (plain) hipLaunchKernelGGL(mppi_batch_noise_kernel, dim3(g, (unsigned)b.E), dim3(256), 0, st, b, k_offset);
+  else hipLaunchKernelGGL(mppi_batch_noise_plan_kernel, dim3(g, (unsigned)b.E), dim3(256), 0, st, b, k_offset, np);
   return hipGetLastError();
 }
 

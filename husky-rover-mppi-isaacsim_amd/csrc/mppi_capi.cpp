@@ -188,6 +188,24 @@ std::string critics_error(const mppi_critics& k, int H) {
   return std::string();
 }
 
+std::string sampling_error(const mppi_sampling& s, int64_t k_offset) {
+  if (s.antithetic != 0 && s.antithetic != 1) return "antithetic must be 0 or 1, got " + std::to_string(s.antithetic);
+  if (s.nominal != 0 && s.nominal != 1) return "nominal must be 0 or 1, got " + std::to_string(s.nominal);
+  if (!std::isfinite(s.beta) || !(s.beta >= 0.0f) || !(s.beta < 1.0f)) return "beta must be finite and in [0, 1)";
+  if (s.antithetic && (k_offset & 1))
+    return "antithetic needs an even k_offset (a pair is global k, k + 1), got " + std::to_string(k_offset);
+  return std::string();
+}
+
+SamplePlan device_plan(const mppi_sampling& s) {
+  SamplePlan r;
+  r.antithetic = s.antithetic;
+  r.nominal = s.nominal;
+  r.beta = s.beta;
+  r.g = (float)std::sqrt(1.0 - (double)s.beta * (double)s.beta);
+  return r;
+}
+
 void fill_rollout(const mppi_ctx* c, const Plan& pl, const mppi_state& st, uint64_t step,
                   const float* unom, RolloutArgs& a) {
   const mppi_params& p = c->p;
@@ -453,6 +471,7 @@ static int launch_server(mppi_ctx* c, unsigned seq) {
   z.wait_ticks = c->srv.fin_wait_ticks;
   z.idle_ticks = c->srv.idle_us * 100;
   z.exit_after = c->srv.exit_after;
+  z.plan = (unsigned)c->samp.antithetic | ((unsigned)c->samp.nominal << 1);  // (set_sampling stops the server)
   c->srv.exit_after = 0;  // (the hook applies to one launch)
   HIP_TRY(launch_step_server(a, z, c->srv.lds, c->stream, c->srv.proj));
   c->srv.running = true;
@@ -581,7 +600,7 @@ static int eps_for_step(mppi_ctx* c, const Plan& pl, uint64_t step, hipStream_t 
     if (rc) return rc;
     slot = 0;
     ns.pol.forget_steps();
-    HIP_TRY(launch_noise(c->p.seed, step * nb, c->p.k_offset, pl.blocks, H_of(c), ns.buf[slot], st, noise_groups(c)));
+    HIP_TRY(launch_noise(c->p.seed, step * nb, c->p.k_offset, pl.blocks, H_of(c), ns.buf[slot], st, noise_groups(c), device_plan(c->samp)));
     ns.pol.mark_ready(slot, step);
     if (sync) HIP_TRY(hipStreamSynchronize(st));
   } else {  // generated on the noise stream: before this rollout
@@ -610,7 +629,7 @@ static int speculate_eps(mppi_ctx* c, const Plan& pl, uint64_t step, int used, h
       waited = true;
     }
     HIP_TRY(launch_noise(c->p.seed, target * nb, c->p.k_offset, pl.blocks, H_of(c), c->ns.buf[slot], c->ns.stream,
-                         noise_groups(c)));
+                         noise_groups(c), device_plan(c->samp)));
     HIP_TRY(hipEventRecord(c->ns.ev[slot], c->ns.stream));
     c->ns.pol.mark_pending(slot, target);
   }
@@ -878,6 +897,9 @@ static void trace_mark(mppi_ctx* c, int k) {
 
 static bool server_shape(const mppi_ctx* c, const Plan& pl, int mode, int* P, int* ncol, int* groups, size_t* lds) {
   // (every workgroup of the server must be resident at once: one rollout block per CU at most)
+  // (beta > 0: the generator's serial form is a whole step's Philox blocks per wave, which the
+  // server's static shares of single blocks cannot hold: such a plan runs as separate launches)
+  if (c->samp.beta > 0.0f) return false;
   if (!c->srv.resident || mode != 0 || !pl.roles || !c->colfin || c->tm.mode != 0 || pl.blocks < 1 ||
       pl.blocks > std::max(c->num_cus, 1))
     return false;
@@ -920,7 +942,7 @@ static int server_step(mppi_ctx* c, int proj, uint64_t step, const Plan& pl, int
     if (v < 0) return fail(MPPI_ESTATE, "no free noise slot");
     if (d == 1 || !srv_noise) {
       HIP_TRY(launch_noise(c->p.seed, target * nb, c->p.k_offset, pl.blocks, H_of(c), c->ns.buf[v], c->ns.stream,
-                           noise_groups(c)));
+                           noise_groups(c), device_plan(c->samp)));
       HIP_TRY(hipEventRecord(c->ns.ev[v], c->ns.stream));
       c->ns.pol.mark_pending(v, target);
     } else {
@@ -1407,6 +1429,24 @@ int mppi_set_critics(mppi_ctx* c, const mppi_critics* k) {
 int mppi_get_critics(mppi_ctx* c, mppi_critics* out) {
   if (!c || !out) return fail(MPPI_EINVAL, "null argument");
   *out = c->crit;
+  return MPPI_OK;
+}
+
+int mppi_set_sampling(mppi_ctx* c, const mppi_sampling* s) {
+  if (!c || !s) return fail(MPPI_EINVAL, "null argument");
+  if (int rc_q = quiesce(c)) return rc_q;  // the next server launch carries the plan
+  const std::string err = sampling_error(*s, c->p.k_offset);
+  if (!err.empty()) return fail(MPPI_EINVAL, "set_sampling: " + err);
+  // the normals generated ahead were drawn under the old plan: no slot holds a step any more (fills
+  // still in flight are waited for before their slot is written again, eps_for_step)
+  c->ns.pol.forget_steps();
+  c->samp = *s;
+  return MPPI_OK;
+}
+
+int mppi_get_sampling(mppi_ctx* c, mppi_sampling* out) {
+  if (!c || !out) return fail(MPPI_EINVAL, "null argument");
+  *out = c->samp;
   return MPPI_OK;
 }
 

@@ -51,6 +51,9 @@ struct mppi_batch {
   // the variant rows' critic sets (mppi_batch_set_variant_critics): row i belongs to variant row i
   std::vector<mppi_critics> critics;         // as last set
   DeviceBuf<BatchCriticRow> d_crit;          // [kBatchMaxVariants], rows past the set: slope_mode -1
+  // the variant rows' sampling plans (mppi_batch_set_variant_sampling): row i belongs to variant row i
+  std::vector<mppi_sampling> sampling;       // as last set
+  DeviceBuf<SamplePlan> d_samp;              // [kBatchMaxVariants], rows past the set: antithetic -1
   // [E] x, y, goal_x, goal_y of each episode when its most recent run began (mppi_batch_score)
   std::vector<std::array<float, 4>> origin;
   // per-episode scenes and trajectory counts (mppi_batch_set_dem / _set_costmap / _set_episode_scene /
@@ -244,6 +247,14 @@ void step_args(mppi_ctx* c, const Plan& pl, RolloutArgs& a, FinishArgs& f) {
   f.mode = 2;
 }
 
+// The noise launch's plans: the context's as it is now, and the rows' table while rows are set.
+BatchNoisePlan noise_plan(const mppi_batch* b) {
+  BatchNoisePlan np;
+  np.ctx = device_plan(b->c->samp);
+  np.rows = b->sampling.empty() ? nullptr : b->d_samp.get();
+  return np;
+}
+
 // The batch's own part of the kernels' arguments: no variant table, no scene table and no log yet.
 BatchArgs batch_args(mppi_batch* b, int proj, const mppi_loop_policy& pol) {
   const mppi_ctx* c = b->c;
@@ -332,7 +343,7 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
     const int m = std::min(every, n_steps - done);
     for (int i = 0; i < m; ++i) {
-      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
       // one rollout launch per projection in use (a workgroup of the other projection's episode
       // returns at once); without variants that is the run's projection alone
       for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
@@ -422,7 +433,7 @@ int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in, bool 
   } else {
     HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
   }
-  HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+  HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
   for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
     if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
   if (tracked)
@@ -620,7 +631,7 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
   for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
     const int m = std::min(every, n_steps - done);
     for (int i = 0; i < m; ++i) {
-      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream));
+      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
       for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
         if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
       if (wheel_form && b->scored)
@@ -1181,6 +1192,31 @@ int mppi_batch_set_variant_critics(mppi_batch* b, int32_t n, const mppi_critics*
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   b->critics.assign(rows, rows + n);
+  return MPPI_OK;
+}
+
+int mppi_batch_set_variant_sampling(mppi_batch* b, int32_t n, const mppi_sampling* rows) {
+  if (!b) return fail(MPPI_EINVAL, "null batch");
+  mppi_ctx* c = b->c;
+  if (int rc_q = quiesce(c)) return rc_q;
+  if (n < 0 || n > kBatchMaxVariants)
+    return fail(MPPI_EINVAL, "batch: need 0 <= n <= " + std::to_string(kBatchMaxVariants) + " sampling rows");
+  if (n > 0 && !rows) return fail(MPPI_EINVAL, "null argument");
+  for (int i = 0; i < n; ++i) {
+    const std::string err = sampling_error(rows[i], c->p.k_offset);
+    if (!err.empty()) return fail(MPPI_EINVAL, "batch: sampling row " + std::to_string(i) + ": " + err);
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (no run of the batch is in flight: every call waits)
+  if (n > 0) {
+    if (!b->d_samp && b->d_samp.alloc(kBatchMaxVariants * sizeof(SamplePlan)))
+      return fail(MPPI_EHIP, "batch: sampling table allocation failed");
+    std::vector<SamplePlan> tab(kBatchMaxVariants, SamplePlan{-1, 0, 0.0f, 1.0f});
+    for (int i = 0; i < n; ++i) tab[i] = device_plan(rows[i]);
+    HIP_TRY(hipMemcpyAsync(b->d_samp, tab.data(), tab.size() * sizeof(SamplePlan), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  b->sampling.assign(rows, rows + n);
   return MPPI_OK;
 }
 

@@ -258,6 +258,7 @@ struct LastStep {
 struct mppi_ctx {
   mppi_params p{};
   mppi_critics crit{MPPI_SLOPE_WHEELS, 0.0f};  // the critic set (mppi_set_critics)
+  mppi_sampling samp{0, 0, 0.0f};              // the sampling plan (mppi_set_sampling)
   int device = 0;
   mppi::Stream stream;  // owned, or the caller's (mppi_set_stream)
   int prio_least = 0, prio_greatest = 0;
@@ -305,6 +306,10 @@ Plan make_plan(const mppi_ctx* c);
 int quiesce(mppi_ctx* c);
 // empty when the set is valid for a context of H steps, else the message naming the field
 std::string critics_error(const mppi_critics& k, int H);
+// the same for a sampling plan on a context whose trajectory 0 is global k_offset
+std::string sampling_error(const mppi_sampling& s, int64_t k_offset);
+// the plan as the generator takes it (g formed here, once)
+SamplePlan device_plan(const mppi_sampling& s);
 int verified_reciprocal(mppi_ctx* c, float b, float* y_out);
 void state_fields(const mppi_params& p, const mppi_state& st, ServerCmd& d);
 void fill_rollout(const mppi_ctx* c, const Plan& pl, const mppi_state& st, uint64_t step, const float* unom,

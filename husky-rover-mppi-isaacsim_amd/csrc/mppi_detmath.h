@@ -345,6 +345,27 @@ MPPI_HD void noise_block(uint64_t seed, uint64_t n, uint64_t k, float* a1, float
   dm_box_muller(r.z, r.w, b1, b2);
 }
 
+// ------------------------------------------------------------------ sampling plan
+// How the base normals z[k, t, c] of the blocks above become a step's sampling normals
+// (mppi_sampling, include/mppi.h; the numpy statement is mppi_amd/sampling.py).  `g` is
+// (float)sqrt(1 - beta^2), formed once on the host.  In this order:
+//   correlation (beta > 0): e[0] = z[0], e[t] = (beta e[t-1]) + (g z[t]), three roundings;
+//   antithetic: an odd global k takes the draw of k - 1 (plan_source) with the sign flipped;
+//   nominal: global k = 0 gets +0 for every t and c (k = 1 then reflects its un-zeroed draw).
+// the global trajectory whose Philox stream trajectory k reads
+MPPI_HD uint64_t plan_source(uint64_t k, int antithetic) { return antithetic ? k & ~(uint64_t)1 : k; }
+// the elementwise part, on the (correlated) normal e of plan_source(k): the exact sign flip and the zero
+MPPI_HD float plan_apply(float e, uint64_t k, int antithetic, int nominal) {
+  const uint32_t flip = (antithetic && (k & 1)) ? 0x80000000u : 0u;
+  const float r = bits_f(f_bits(e) ^ flip);
+  return (nominal && k == 0) ? 0.0f : r;
+}
+// one step of the recurrence (the products are rounded on their own: no contraction)
+MPPI_HD float plan_ar1(float prev, float z, float beta, float g) {
+  const float a = beta * prev, b = g * z;
+  return a + b;
+}
+
 // ------------------------------------------------------------------ atan2 (float64)
 // The arctangent of the path metrics (mppi_path_metrics.h; MPPI_isaac.py:246 np.arctan2), DEFINED as a
 // fixed sequence of IEEE float64 + - * / sqrt, so the device and the numpy restatement

@@ -174,7 +174,9 @@ struct ServerArgs {
   uint64_t idle_ticks;        // the head leaves after this long without a command (and relays the stop)
   unsigned exit_after;        // test hook (0: off): the head leaves at its poll after serving this many
                               // commands, whether or not the next one was posted
-  uint64_t* clk;             // optional: the server stamps [kClkServer, kClkServer + 4) of RolloutArgs::clk
+  unsigned plan;              // the sampling plan's elementwise part for the noise phase: bit 0 antithetic,
+                              // bit 1 nominal (in the padding behind exit_after: no other offset moved)
+  uint64_t* clk;            // optional: the server stamps [kClkServer, kClkServer + 4) of RolloutArgs::clk
 };
 hipError_t launch_step_server(const RolloutArgs& a, const ServerArgs& z, size_t lds, hipStream_t st, int proj);
 // record tree finish (mppi_finish_kernel): the fallback where the column-split shape does not fit
@@ -197,8 +199,18 @@ hipError_t launch_hold(int groups, size_t lds, uint64_t ticks, hipStream_t st);
 hipError_t launch_cdiv_verify(float b, float y, unsigned* bad, hipStream_t st);
 // The sampling normals of one step (Philox block n_base + t/2 of global trajectory k_offset + k),
 // laid out [blocks][2][H][256]: eps1 rows then eps2 rows, 256 trajectories per row.
+// A sampling plan as the generator takes it: mppi_sampling (include/mppi.h) and g = (float)sqrt(1 -
+// beta^2) in float64, formed once on the host (the semantics: mppi_detmath.h).  In the
+// batch's table (BatchNoisePlan::rows) antithetic -1 marks a row the caller did not give.
+struct SamplePlan {
+  int antithetic, nominal;
+  float beta, g;
+};
+// `plan`: the sampling plan; the default plan launches the kernel as it was,
+// antithetic / nominal its elementwise form, beta > 0 the serial form (one wave per leaf block and 64
+// trajectories, which walks the step's Philox blocks in order).
 hipError_t launch_noise(uint64_t seed, uint64_t n_base, int64_t k_offset, int blocks, int H, float* eps,
-                        hipStream_t st, int max_groups);
+                        hipStream_t st, int max_groups, const SamplePlan& plan);
 // ---- batched closed-loop episodes (mppi_batch_*) ----
 // E independent episodes over one context's parameters and (unless an episode holds a scene slot of
 // the batch) scene, advanced by three stream-ordered
@@ -281,7 +293,13 @@ struct BatchArgs {
 // (the scene pointer took the place of two paddings: the kernels' argument segment did not grow)
 static_assert(sizeof(BatchArgs) == 144, "BatchArgs layout");
 constexpr int kBatchMaxRecords = 16;  // leaf records per episode: the finish's tree is one LDS pass
-hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st);
+// The noise launch's sampling plans: the context's, and the table of the variant rows' plans
+// (mppi_batch_set_variant_sampling; null: none set), [kBatchMaxVariants], read behind the variant index.
+struct BatchNoisePlan {
+  SamplePlan ctx;
+  const SamplePlan* rows;
+};
+hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st, const BatchNoisePlan& np);
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);
 hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st);
 // ---- the task queue of a batch (mppi_batch_set_tasks / _run_tasks) ----

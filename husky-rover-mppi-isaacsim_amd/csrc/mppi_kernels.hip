@@ -750,10 +750,22 @@ __device__ __forceinline__ int thread_id() {
 struct NoiseVals {
   float a1, a2, b1, b2;
 };
-__device__ __forceinline__ NoiseVals noise_gen(uint64_t seed, uint64_t n_base, int64_t k_offset, int blk, int n, int tj) {
+// PLAN: the elementwise part of a sampling plan (mppi_detmath.h plan_source / plan_apply, the plan
+// words wave-uniform); false: the default plan, the generator as it was before there was a choice.
+template <bool PLAN = false>
+__device__ __forceinline__ NoiseVals noise_gen(uint64_t seed, uint64_t n_base, int64_t k_offset, int blk, int n, int tj,
+                                               int anti = 0, int nominal = 0) {
   const uint64_t kg = (uint64_t)(k_offset + (int64_t)blk * 256 + tj);
   NoiseVals v;
-  noise_block_pk(seed, n_base + (uint64_t)n, kg, &v.a1, &v.a2, &v.b1, &v.b2);
+  if constexpr (PLAN) {
+    noise_block_pk(seed, n_base + (uint64_t)n, plan_source(kg, anti), &v.a1, &v.a2, &v.b1, &v.b2);
+    v.a1 = plan_apply(v.a1, kg, anti, nominal);
+    v.a2 = plan_apply(v.a2, kg, anti, nominal);
+    v.b1 = plan_apply(v.b1, kg, anti, nominal);
+    v.b2 = plan_apply(v.b2, kg, anti, nominal);
+  } else {
+    noise_block_pk(seed, n_base + (uint64_t)n, kg, &v.a1, &v.a2, &v.b1, &v.b2);
+  }
   return v;
 }
 __device__ __forceinline__ void noise_store(float* __restrict__ eps, int H, int blk, int n, int tj, const NoiseVals& v) {
@@ -767,21 +779,24 @@ __device__ __forceinline__ void noise_store(float* __restrict__ eps, int H, int 
     __hip_atomic_store(e2 + 256, v.b2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
+template <bool PLAN = false>
 __device__ __forceinline__ void noise_unit(uint64_t seed, uint64_t n_base, int64_t k_offset, int H, int blk, int n,
-                                           float* __restrict__ eps, int tj) {
-  noise_store(eps, H, blk, n, tj, noise_gen(seed, n_base, k_offset, blk, n, tj));
+                                           float* __restrict__ eps, int tj, int anti = 0, int nominal = 0) {
+  noise_store(eps, H, blk, n, tj, noise_gen<PLAN>(seed, n_base, k_offset, blk, n, tj, anti, nominal));
 }
 // units g0, g0 + gstride, ... below `end` (unit g = block g / NB, Philox block g % NB), the block and
 // Philox index carried from unit to unit (wave-uniform: no 64-bit division per unit; g < 2^31,
 // mppi_create bounds K)
+template <bool PLAN = false>
 __device__ __forceinline__ void noise_rows(uint64_t seed, uint64_t n_base, int64_t k_offset, int H, int end,
-                                           float* __restrict__ eps, int g0, int gstride, int tj) {
+                                           float* __restrict__ eps, int g0, int gstride, int tj, int anti = 0,
+                                           int nominal = 0) {
   const int NB = (H + 1) >> 1;
   if (g0 >= end) return;
   int blk = g0 / NB, n = g0 - blk * NB;
   const int sq = gstride / NB, sr = gstride - sq * NB;
   for (int g = g0; g < end; g += gstride) {
-    noise_unit(seed, n_base, k_offset, H, blk, n, eps, tj);
+    noise_unit<PLAN>(seed, n_base, k_offset, H, blk, n, eps, tj, anti, nominal);
     blk += sq;
     n += sr;
     if (n >= NB) {
@@ -805,8 +820,10 @@ __device__ __forceinline__ void noise_pos_step(NoisePos& p, int stride, int NB) 
     ++p.blk;
   }
 }
+template <bool PLAN = false>
 __device__ __forceinline__ void noise_waves(uint64_t seed, uint64_t n_base, int64_t k_offset, int H, int q, int q1,
-                                            int stride, float* __restrict__ eps, int lane) {
+                                            int stride, float* __restrict__ eps, int lane, int anti = 0,
+                                            int nominal = 0) {
   const int NB = (H + 1) >> 1;
   if (q >= q1) return;
   NoisePos a;
@@ -819,14 +836,42 @@ __device__ __forceinline__ void noise_waves(uint64_t seed, uint64_t n_base, int6
     noise_pos_step(b, stride, NB);
     const bool has_b = b.q < q1;
     if (!has_b) b = a;  // (computed, not stored)
-    const NoiseVals va = noise_gen(seed, n_base, k_offset, a.blk, a.n, ((a.q & 3) << 6) + lane);
-    const NoiseVals vb = noise_gen(seed, n_base, k_offset, b.blk, b.n, ((b.q & 3) << 6) + lane);
+    const NoiseVals va = noise_gen<PLAN>(seed, n_base, k_offset, a.blk, a.n, ((a.q & 3) << 6) + lane, anti, nominal);
+    const NoiseVals vb = noise_gen<PLAN>(seed, n_base, k_offset, b.blk, b.n, ((b.q & 3) << 6) + lane, anti, nominal);
     noise_store(eps, H, a.blk, a.n, ((a.q & 3) << 6) + lane, va);
     if (!has_b) break;
     noise_store(eps, H, b.blk, b.n, ((b.q & 3) << 6) + lane, vb);
     a = b;
     noise_pos_step(a, stride, NB);
     if (a.q >= q1) break;
+  }
+}
+
+// The serial form, for a plan with beta > 0 (plan_ar1): the unit is wave-unit u = (leaf block u / 4,
+// trajectories 64 (u % 4) .. + 63), which walks its NB Philox blocks in order and carries e[t - 1]
+// per lane and channel; units u0, u0 + stride, ... below u1.  The sign and the zero come after the
+// recurrence (plan_apply on the stored value only).
+__device__ __forceinline__ void noise_serial(uint64_t seed, uint64_t n_base, int64_t k_offset, int H, int u0, int u1,
+                                             int stride, float* __restrict__ eps, int lane, const SamplePlan pl) {
+  const int NB = (H + 1) >> 1;
+  for (int u = u0; u < u1; u += stride) {
+    const int blk = u >> 2, tj = ((u & 3) << 6) + lane;
+    const uint64_t kg = (uint64_t)(k_offset + (int64_t)blk * 256 + tj);
+    const uint64_t ks = plan_source(kg, pl.antithetic);
+    float e1 = 0.0f, e2 = 0.0f;
+    for (int n = 0; n < NB; ++n) {
+      NoiseVals z, v;
+      noise_block_pk(seed, n_base + (uint64_t)n, ks, &z.a1, &z.a2, &z.b1, &z.b2);
+      e1 = n == 0 ? z.a1 : plan_ar1(e1, z.a1, pl.beta, pl.g);
+      e2 = n == 0 ? z.a2 : plan_ar1(e2, z.a2, pl.beta, pl.g);
+      v.a1 = plan_apply(e1, kg, pl.antithetic, pl.nominal);
+      v.a2 = plan_apply(e2, kg, pl.antithetic, pl.nominal);
+      e1 = plan_ar1(e1, z.b1, pl.beta, pl.g);  // (step 2n + 1 = H of an odd H: computed, not stored)
+      e2 = plan_ar1(e2, z.b2, pl.beta, pl.g);
+      v.b1 = plan_apply(e1, kg, pl.antithetic, pl.nominal);
+      v.b2 = plan_apply(e2, kg, pl.antithetic, pl.nominal);
+      noise_store(eps, H, blk, n, tj, v);
+    }
   }
 }
 
@@ -3678,6 +3723,21 @@ __global__ __launch_bounds__(256) void mppi_noise_kernel(uint64_t seed, uint64_t
                                                          int H, int n_blocks, float* __restrict__ eps) {
   noise_rows(seed, n_base, k_offset, H, n_blocks * ((H + 1) >> 1), eps, blockIdx.x, gridDim.x, threadIdx.x);
 }
+// a sampling plan's elementwise part (antithetic / nominal) on the same units
+__global__ __launch_bounds__(256) void mppi_noise_plan_kernel(uint64_t seed, uint64_t n_base, int64_t k_offset,
+                                                              int H, int n_blocks, float* __restrict__ eps, int anti,
+                                                              int nominal) {
+  noise_rows<true>(seed, n_base, k_offset, H, n_blocks * ((H + 1) >> 1), eps, blockIdx.x, gridDim.x, threadIdx.x,
+                   anti, nominal);
+}
+// beta > 0: the serial form, wave w of workgroup g takes the wave-units 4 g + w, + 4 G, ...
+__global__ __launch_bounds__(256) void mppi_noise_serial_kernel(uint64_t seed, uint64_t n_base, int64_t k_offset,
+                                                                int H, int n_blocks, float* __restrict__ eps,
+                                                                const SamplePlan pl) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  noise_serial(seed, n_base, k_offset, H, (int)blockIdx.x * 4 + wave, n_blocks * 4, (int)gridDim.x * 4, eps,
+               (int)threadIdx.x & 63, pl);
+}
 
 // =====================================================================  resident step server
 // One launch serves a sequence of sampled steps (mppi_capi.cpp "resident step server"): workgroup b
@@ -3719,7 +3779,10 @@ __device__ __forceinline__ const ServerLaunch* fresh_args() {
 // for the server's idle exit on every step: 359 launches instead of 3 for 220 steps and half the
 // headline (profiles/leaf_sparse_notes.md).  The cap costs one dword spilled at entry and reloaded
 // once per step, outside the rollout.
-template <int TB, int PROJ, bool ALT>
+// PLAN: the launch's sampling plan has an elementwise part (ServerArgs::plan != 0: antithetic / nominal;
+// mppi_set_sampling stops the server, so a launch's plan is fixed); false: the default plan, and the
+// kernel is the one it was before there was a choice (a plan with beta > 0 never runs here).
+template <int TB, int PROJ, bool ALT, bool PLAN>
 __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) void mppi_step_server_kernel(
     const ServerLaunch args) {
   __shared__ unsigned cmd_lds[32];
@@ -3848,7 +3911,11 @@ __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) v
       __builtin_amdgcn_s_setprio(0);
       const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
       const int q0 = (int)(W * (2 * ticket) / S), q1 = (int)(W * (2 * ticket + 2) / S);
-      noise_waves(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63);
+      if constexpr (PLAN)
+        noise_waves<true>(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63,
+                          (int)(z.plan & 1u), (int)(z.plan >> 1));
+      else
+        noise_waves(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63);
     }
     if (blk >= 0) {
       __builtin_amdgcn_s_setprio(0);  // the rollout waves' priorities do not carry into the finish
@@ -3905,7 +3972,11 @@ __global__ __launch_bounds__(NROLES * TB) __attribute__((amdgpu_num_vgpr(56))) v
       if (nslot >= 0 && blk < z.fin_groups - 1) {  // its share of the normals of step + 2 (see above)
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int q0 = (int)(W * (2 * nn + blk) / S), q1 = (int)(W * (2 * nn + blk + 1) / S);
-        noise_waves(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63);
+        if constexpr (PLAN)
+          noise_waves<true>(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63,
+                            (int)(z.plan & 1u), (int)(z.plan >> 1));
+        else
+          noise_waves(a.seed, nbase, a.k_offset, a.H, q0 + wave, q1, NROLES * TB / 64, z.eps[nslot], tid & 63);
       }
     }
     // this CU's L1 forgets the step's normals rows before a later step reads rewritten ones
@@ -3926,25 +3997,36 @@ hipError_t launch_step_server(const RolloutArgs& a, const ServerArgs& z, size_t 
   const dim3 g((unsigned)z.nroll), b(NROLES * 256);
   // (the launch's critic set is fixed: mppi_set_critics stops the server)
   const bool alt = a.slope_body || a.w_orient != 0.0f;
+  const bool plan = z.plan != 0;  // (and the launch's sampling plan: mppi_set_sampling stops the server too)
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g, b, lds, st, ServerLaunch{a, z}); };
   if (proj == 3) {
-    if (alt) hipLaunchKernelGGL((mppi_step_server_kernel<256, 3, true>), g, b, lds, st, ServerLaunch{a, z});
-    else hipLaunchKernelGGL((mppi_step_server_kernel<256, 3, false>), g, b, lds, st, ServerLaunch{a, z});
+    if (alt) plan ? go(mppi_step_server_kernel<256, 3, true, true>) : go(mppi_step_server_kernel<256, 3, true, false>);
+    else plan ? go(mppi_step_server_kernel<256, 3, false, true>) : go(mppi_step_server_kernel<256, 3, false, false>);
   } else {
-    if (alt) hipLaunchKernelGGL((mppi_step_server_kernel<256, 2, true>), g, b, lds, st, ServerLaunch{a, z});
-    else hipLaunchKernelGGL((mppi_step_server_kernel<256, 2, false>), g, b, lds, st, ServerLaunch{a, z});
+    if (alt) plan ? go(mppi_step_server_kernel<256, 2, true, true>) : go(mppi_step_server_kernel<256, 2, true, false>);
+    else plan ? go(mppi_step_server_kernel<256, 2, false, true>) : go(mppi_step_server_kernel<256, 2, false, false>);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_noise(uint64_t seed, uint64_t n_base, int64_t k_offset, int blocks, int H, float* eps,
-                        hipStream_t st, int max_groups) {
+                        hipStream_t st, int max_groups, const SamplePlan& plan) {
   // Grid capped (max_groups, a few workgroups per CU): the noise of step i+2 is generated
   // while the finish of step i runs and the next rollout starts; a full-size grid fills every
   // wave slot ahead of their 16-wave workgroups, which then wait for the whole noise kernel.
   const int NB = (H + 1) >> 1;
   const int64_t total = (int64_t)blocks * NB;
   const unsigned grid = (unsigned)std::min<int64_t>(total, std::max(max_groups, 1));
-  hipLaunchKernelGGL(mppi_noise_kernel, dim3(grid), dim3(256), 0, st, seed, n_base, k_offset, H, blocks, eps);
+  if (plan.beta > 0.0f) {  // one wave per (leaf block, 64 trajectories): blocks workgroups at the most
+    const unsigned sg = (unsigned)std::min<int64_t>(blocks, std::max(max_groups, 1));
+    hipLaunchKernelGGL(mppi_noise_serial_kernel, dim3(sg), dim3(256), 0, st, seed, n_base, k_offset, H, blocks, eps,
+                       plan);
+  } else if (plan.antithetic || plan.nominal) {
+    hipLaunchKernelGGL(mppi_noise_plan_kernel, dim3(grid), dim3(256), 0, st, seed, n_base, k_offset, H, blocks, eps,
+                       plan.antithetic, plan.nominal);
+  } else {
+    hipLaunchKernelGGL(mppi_noise_kernel, dim3(grid), dim3(256), 0, st, seed, n_base, k_offset, H, blocks, eps);
+  }
   return hipGetLastError();
 }
 

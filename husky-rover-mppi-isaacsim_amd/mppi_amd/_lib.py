@@ -98,6 +98,11 @@ class MppiCritics(C.Structure):
     _fields_ = [("slope_mode", C.c_int32), ("w_orientation", C.c_float)]
 
 
+class MppiSampling(C.Structure):
+    """mppi_sampling: the sampling plan of a context or of a variant row (12 bytes)."""
+    _fields_ = [("antithetic", C.c_int32), ("nominal", C.c_int32), ("beta", C.c_float)]
+
+
 COST_TERMS = ("path", "slope", "speed", "obstacle")   # mppi_cost_term order (include/mppi.h)
 COST_TERMS5 = COST_TERMS + ("orientation",)           # mppi_get_cost_terms5
 SLOPE_MODES = {"wheels": 0, "body": 1}                # mppi_slope_mode
@@ -134,6 +139,9 @@ _PROTOS = {
     "mppi_set_critics": (C.c_int, [C.c_void_p, C.POINTER(MppiCritics)]),
     "mppi_get_critics": (C.c_int, [C.c_void_p, C.POINTER(MppiCritics)]),
     "mppi_batch_set_variant_critics": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiCritics)]),
+    "mppi_set_sampling": (C.c_int, [C.c_void_p, C.POINTER(MppiSampling)]),
+    "mppi_get_sampling": (C.c_int, [C.c_void_p, C.POINTER(MppiSampling)]),
+    "mppi_batch_set_variant_sampling": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MppiSampling)]),
     "mppi_get_score_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_set_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "mppi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
@@ -792,6 +800,19 @@ class Engine:
         self._c(self.lib.mppi_get_critics(self.ctx, C.byref(k)), "mppi_get_critics")
         return critics_as_dict(k)
 
+    def set_sampling(self, antithetic=False, nominal=False, beta=0.0):
+        """mppi_set_sampling: how the K control sequences are drawn from the next step on (mppi_amd.sampling):
+        antithetic pairs, a noise-free rollout of the shifted nominal as trajectory 0, AR(1) noise of
+        coefficient beta in [0, 1).  The default changes no bit."""
+        k = make_sampling(antithetic, nominal, beta, k_offset=int(self.params.k_offset))
+        self._c(self.lib.mppi_set_sampling(self.ctx, C.byref(k)), "mppi_set_sampling")
+
+    def get_sampling(self):
+        """mppi_get_sampling: dict(antithetic, nominal, beta)."""
+        k = MppiSampling()
+        self._c(self.lib.mppi_get_sampling(self.ctx, C.byref(k)), "mppi_get_sampling")
+        return dict(antithetic=bool(k.antithetic), nominal=bool(k.nominal), beta=float(k.beta))
+
     def detmath_atan2(self, y, x):
         """mppi_detmath_atan2: (dm_atan2(y, x) as the device computes it, the device library's atan2(y, x)),
         float64 arrays of y's shape (y and x broadcast)."""
@@ -901,6 +922,14 @@ def make_critics(slope="wheels", w_orientation=0.0):
     if not (np.isfinite(w) and abs(w) <= float(np.finfo(np.float32).max)):
         raise ValueError(f"w_orientation must be a finite float32, got {w_orientation!r}")
     return MppiCritics(mode, w)
+
+
+def make_sampling(antithetic=False, nominal=False, beta=0.0, k_offset=None):
+    """Fill mppi_sampling; ValueError names the field (the checks of mppi_set_sampling; the one on
+    k_offset where the caller gives it)."""
+    from .sampling import make_plan
+    p = make_plan(antithetic, nominal, beta, k_offset)
+    return MppiSampling(int(p["antithetic"]), int(p["nominal"]), p["beta"])
 
 
 def critics_as_dict(k: MppiCritics):
@@ -1064,7 +1093,9 @@ class Batch:
     def set_variants(self, variants):
         """The batch's variant table: a list of MppiBatchVariant or dicts (make_variant's arguments);
         an empty list clears it."""
-        from .batch import split_variant
+        from .batch import split_sampling, split_variant
+        plans = [(v, None) if isinstance(v, MppiBatchVariant) else split_sampling(v) for v in variants]
+        variants = [v for v, _ in plans]
         split = [(v, None) if isinstance(v, MppiBatchVariant) else split_variant(v) for v in variants]
         rows = [_as_variant(v) for v, _ in split]
         arr = (MppiBatchVariant * max(len(rows), 1))(*rows)
@@ -1074,6 +1105,20 @@ class Batch:
         crit = [k for _, k in split]
         self.set_variant_critics([self.engine.critics() if k is None else k for k in crit]
                                  if any(k is not None for k in crit) else [])
+
+        # and with "antithetic" / "nominal" / "noise_beta" keys the sampling rows, by the same rule
+        samp = [k for _, k in plans]
+        self.set_variant_sampling([self.engine.get_sampling() if k is None else k for k in samp]
+                                  if any(k is not None for k in samp) else [])
+
+    def set_variant_sampling(self, rows):
+        """mppi_batch_set_variant_sampling: variant row i runs with the sampling plan rows[i] (MppiSampling
+        or dict(antithetic=, nominal=, beta=)); variants past the list, and episodes or tasks without a
+        variant, run with the engine's plan.  An empty list clears the rows."""
+        rows = [k if isinstance(k, MppiSampling) else make_sampling(**dict(k)) for k in rows]
+        arr = (MppiSampling * max(len(rows), 1))(*rows)
+        _check(self.lib, self.lib.mppi_batch_set_variant_sampling(self.h, len(rows), arr),
+               "mppi_batch_set_variant_sampling")
 
     def set_variant_critics(self, rows):
         """mppi_batch_set_variant_critics: variant row i runs with critic set rows[i] (MppiCritics or
@@ -1537,6 +1582,11 @@ class Group:
     def set_critics(self, slope="wheels", w_orientation=0.0):
         """The critic set of every member (Engine.set_critics)."""
         self._each("set_critics", slope, w_orientation)
+
+    def set_sampling(self, antithetic=False, nominal=False, beta=0.0):
+        """The sampling plan of every member (Engine.set_sampling); the members' k_offset are even
+        (shards are whole leaves), so a pair never straddles two members."""
+        self._each("set_sampling", antithetic, nominal, beta)
 
     def set_async_tail(self, on=True):
         """Deferred optimal rollout on every member (Engine.set_async_tail)."""

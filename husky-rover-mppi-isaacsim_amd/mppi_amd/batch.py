@@ -83,6 +83,24 @@ def split_variant(variant):
     return v, crit
 
 
+SAMPLING_KEYS = ("antithetic", "nominal", "noise_beta")   # mppi_sampling (include/mppi.h) in a variant dict
+
+
+def split_sampling(variant):
+    """A variant dict that may carry the sampling keys -> (the dict without them, the sampling plan).
+
+    "antithetic", "nominal" and "noise_beta" fill the batch's third table
+    (mppi_batch_set_variant_sampling).  The plan is dict(antithetic=, nominal=, beta=) with the
+    default for a key not given, or None when the dict carries none of the keys: that row runs with
+    the controller's plan."""
+    from .sampling import make_plan
+    v = dict(variant)
+    given = {k: v.pop(k) for k in SAMPLING_KEYS if k in v}
+    if not given:
+        return v, None
+    return v, make_plan(given.get("antithetic", False), given.get("nominal", False), given.get("noise_beta", 0.0))
+
+
 def variant_dict(proj="3d", **fields):
     """A full variant dict: the library's default parameters (_lib.make_params) and run()'s sigma
     schedule, overridden by `fields`."""

@@ -18,6 +18,7 @@ import numpy as np
 import yaml
 
 from . import _lib, scene
+from . import sampling as _sampling
 from .batch import campaign_tasks, episode_scenes, to_mppi_state
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -199,7 +200,9 @@ class MPPI_Controller:
     ``max_loops`` (run(), default 3500 as :763), ``async_tail``, ``resident`` (the resident
     step server: true / 1 for back-to-back calls (default), 2 always, false / 0 never;
     mppi_set_option "resident"; env MPPI_RESIDENT wins when set),
-    ``resident_idle_us`` (how long an idle server stays resident, 200: DESIGN.md §3.5).
+    ``resident_idle_us`` (how long an idle server stays resident, 200: DESIGN.md §3.5),
+    ``slope`` / ``w_orientation`` (the critic set) and ``sampling: {antithetic:, nominal:, beta:}``
+    (the sampling plan; ``set_sampling``).
     """
 
     def __init__(self, surface, robot, config_path, goal_x, goal_y, goal_orientation):
@@ -243,6 +246,8 @@ class MPPI_Controller:
         self.resident_idle_us = eng.get("resident_idle_us")
         # the critic set (Engine.set_critics): the slope critic's mode and the orientation weight
         self.critics = dict(slope=eng.get("slope", "wheels"), w_orientation=float(eng.get("w_orientation", 0.0)))
+        # the sampling plan (Engine.set_sampling): engine: {sampling: {antithetic:, nominal:, beta:}}
+        self.sampling = _sampling.make_plan(**dict(eng.get("sampling") or {}))
         self.step_index = 0          # Philox step counter (replaces rng.integers at :517)
         self.engine = None
         self._out = None
@@ -270,6 +275,8 @@ class MPPI_Controller:
         self._tail_fresh = True
         if self.critics != dict(slope="wheels", w_orientation=0.0):
             self.engine.set_critics(**self.critics)
+        if not _sampling.is_default(self.sampling):
+            self.engine.set_sampling(**self.sampling)
         self._upload_dem(self.surface.Z)
         self._upload_costmap(self.surface.costmap)
         H, K = self.number_of_iterations, self.number_of_trajectories
@@ -437,6 +444,13 @@ class MPPI_Controller:
         if self.engine is not None:
             self.engine.set_critics(**self.critics)
             self._cost_terms = None
+
+    def set_sampling(self, antithetic=False, nominal=False, beta=0.0):
+        """The sampling plan of the following steps (Engine.set_sampling, mppi_amd.sampling): antithetic
+        pairs, the noise-free nominal rollout as trajectory 0, AR(1) noise of coefficient beta."""
+        self.sampling = _sampling.make_plan(antithetic, nominal, beta)     # (ValueError before anything changes)
+        if self.engine is not None:
+            self.engine.set_sampling(**self.sampling)
 
     def score_paths(self, traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None, state=None):
         """The critics on caller-supplied paths (Engine.score_paths): logged runs

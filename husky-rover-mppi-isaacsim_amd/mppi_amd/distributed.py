@@ -58,12 +58,14 @@ class ShardedMPPI:
     """
 
     def __init__(self, K_global: int, H: int, device, group=None, engine_factory=None, always_exchange=False,
-                 **params_kw):
+                 sampling=None, **params_kw):
         """``engine_factory(K, H, k_offset, device)`` replaces the HIP engine (CPU protocol tests
         drive the same exchange with an oracle-backed stand-in); ``device="cpu"`` then skips the
         HIP stream and keeps the exchange buffers in host memory (gloo).  ``always_exchange``
         runs the partial step, the collective and the finish even at world size 1 (tests of the
-        RCCL path on a one-GPU host)."""
+        RCCL path on a one-GPU host).  ``sampling``: dict(antithetic=, nominal=, beta=) for
+        Engine.set_sampling on this rank's engine (shards begin on a leaf, so every k_offset is even
+        and an antithetic pair never straddles two ranks; the plan is keyed by the GLOBAL index)."""
         self.always_exchange = bool(always_exchange)
         import contextlib
 
@@ -87,6 +89,8 @@ class ShardedMPPI:
             self.engine = _lib.Engine(_lib.make_params(k_eng, H, k_offset=k_off, **params_kw), device)
         else:
             self.engine = engine_factory(k_eng, H, k_off, device)
+        if sampling is not None:
+            self.engine.set_sampling(**dict(sampling))
         if device == "cpu":
             self.stream = None
             self._ctx = contextlib.nullcontext

@@ -337,6 +337,30 @@ typedef struct mppi_critics { int32_t slope_mode; float w_orientation; } mppi_cr
 int mppi_set_critics(mppi_ctx* ctx, const mppi_critics* critics);   /* default {WHEELS, 0} */
 int mppi_get_critics(mppi_ctx* ctx, mppi_critics* out);
 
+/* ---- the sampling plan ----
+ * How the K control sequences of a step are drawn: u = clamp(u_nom[min(t+1, H-1)] + sigma e[k, t, c])
+ * with e made of the base normals z[k, t, c] (Philox key = seed, block step * ceil(H/2) + t/2,
+ * global trajectory k: unchanged).  src(k) = k & ~1 if `antithetic`, else k.  All float32, no
+ * contraction, in this order:
+ *   beta        in [0, 1): time-correlated (AR(1)) noise.  e[0] = z[src(k), 0, c], e[t] = (beta e[t-1])
+ *               + (g z[src(k), t, c]), three roundings, g = (float)sqrt(1.0 - (double)beta (double)beta).
+ *               0: e = z.
+ *   antithetic  an odd global k takes -e of k - 1 (an exact sign flip, both channels; its own Philox
+ *               stream is unused).  An even k keeps its own draw, with or without a partner.  Needs an
+ *               even k_offset.
+ *   nominal     global k == 0 gets +0.0f for every t and c: it rolls out the clamped shifted nominal
+ *               sequence.  With `antithetic`, k == 1 is the negation of k = 0's un-zeroed sequence.
+ * With the default plan {0, 0, 0} every result keeps its bits.  mppi_set_sampling stops the resident
+ * server like every call outside the step set and drops the normals generated ahead; the plan applies
+ * from the next mppi_step / _step_partial and to mppi_dump_rollouts' re-run of a step taken under it.
+ * mppi_step_injected ignores it.  `antithetic` and `nominal` run on the resident server; with beta > 0
+ * the steps are separate launches (the generator's serial form does not fit the server's static
+ * shares).  Each group member is set through mppi_group_context.  MPPI_EINVAL, naming the field, for a
+ * flag outside {0, 1}, a beta that is not finite or outside [0, 1), or antithetic with an odd k_offset. */
+typedef struct mppi_sampling { int32_t antithetic; int32_t nominal; float beta; } mppi_sampling;  /* 12 bytes */
+int mppi_set_sampling(mppi_ctx* ctx, const mppi_sampling* plan);   /* default {0, 0, 0.0f} */
+int mppi_get_sampling(mppi_ctx* ctx, mppi_sampling* out);
+
 /* ---- path scoring and per-critic terms ----
  * _evaluate_trajectories_kernel (critics_warp.py:302-329) on paths the caller supplies: the
  * offline re-scoring of logged runs (evaluate_trajectory.py, dim = 1, paths of up to 3500
@@ -469,6 +493,12 @@ int  mppi_batch_set_episode_variant(mppi_batch* b, int32_t e, int32_t variant);
  * mppi_set_critics).  The log scorers (mppi_batch_score, _score_tasks) use the context's set: a log
  * has no wheel arrays, so their slope critic is the body form in either mode. */
 int  mppi_batch_set_variant_critics(mppi_batch* b, int32_t n, const mppi_critics* rows);
+/* The sampling plans of the variant rows, by the rules of mppi_batch_set_variant_critics: variant row
+ * i runs with plan row i if i < n; every other variant, and every episode or task without a variant,
+ * runs with the context's plan (mppi_set_sampling) as it is at every run.  Applies to mppi_batch_run,
+ * _run_tasks, _step_device and _step_tracked; every step of such an episode is bitwise the mppi_step of
+ * a context after mppi_set_sampling(row).  MPPI_EINVAL names the row and the field. */
+int  mppi_batch_set_variant_sampling(mppi_batch* b, int32_t n, const mppi_sampling* rows);
 
 /* ---- per-episode scene and trajectory count ----
  * The campaign's other two axes: "various terrain constraints, various number of trajectories"
@@ -777,7 +807,8 @@ int mppi_get_tail_timing(mppi_ctx* ctx, double* tail_ms, int64_t* launches);
  * column-split mppi_colfin_kernel, 0 = record tree mppi_finish_kernel), [7]=records padded
  * (column-split) or records (tree), [8]=columns per finish workgroup, [9]=finish workgroups,
  * [10]=steps whose sampled controls the rollout keeps in LDS, [11]=1 if the step ran on the
- * resident step server (mppi_step_server_kernel), else 0; [12]/[13]/[14] = server launches /
+ * resident step server (mppi_step_server_kernel), else 0 (always 0 under a sampling plan with
+ * beta > 0, whose steps are separate launches); [12]/[13]/[14] = server launches /
  * steps served / failed steps so far (mppi_set_option "resident"); [15] = commands posted to a
  * server that was leaving on its idle limit and served by a relaunch (included in [12]); [16] =
  * failed server steps rerun as separate launches; [17] = steps the server could have run that ran as

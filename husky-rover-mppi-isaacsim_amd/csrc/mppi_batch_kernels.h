@@ -159,6 +159,13 @@ __global__ __launch_bounds__(NROLES * 256) void mppi_batch_rollout_kernel(const 
   roles_body<256, PROJ, 0, false, false, ALT>(a, (int)blockIdx.x, nullptr);
 }
 
+// The goal test (include/mppi.h): inside the tolerance on both axes.  With finite coordinates that is
+// !(|dx| > tol || |dy| > tol); a NaN coordinate is never inside, so a pose that is not a number is not
+// "reached" (DESIGN.md §4 D13).
+__device__ __forceinline__ bool goal_reached(float x, float y, float gx, float gy, float tol) {
+  return fabsf(x - gx) <= tol && fabsf(y - gy) <= tol;
+}
+
 // The critics' scalar parts of an episode at (x, y) with the goal (gx, gy): state_fields() of
 // mppi_capi.cpp, the same float32 operations in the same order (IEEE sqrtf and /).  The one statement
 // of the rule on the device: the claim, the advance lane and the ingest all write them through this.
@@ -199,7 +206,7 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
     }
     const BatchTask* t = q.tasks + i;
     const float x = t->x0, y = t->y0, gx = t->gx, gy = t->gy;
-    if (!(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol)) {
+    if (goal_reached(x, y, gx, gy, b.goal_tol)) {
       BatchTaskResult* r = q.res + i;
       r->x0 = x;
       r->y0 = y;
@@ -617,7 +624,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     ep->cur = cur_buf ^ 1;
     ep->step = ep->step + 1;
     ep->steps_run = row + 1;
-    const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
+    const bool reached = goal_reached(x, y, gx, gy, b.goal_tol);
     // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
     if constexpr (SCORED && WX) {
       score_extend_row_x<true>(sa, *sc, cm, row, x, y, z, v, gx, gy, wx->wacc != nullptr, wa, cw);
@@ -857,7 +864,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
         ep->step = 0;
         if (io.seeds) ep->seed = io.seeds[e];
       }
-      const bool reached = !(fabsf(x - gx) > b.goal_tol || fabsf(y - gy) > b.goal_tol);
+      const bool reached = goal_reached(x, y, gx, gy, b.goal_tol);
       BatchRunResult* o = runs < t.runs_per_episode ? t.results + (size_t)e * t.runs_per_episode + runs : nullptr;
       if (reset || r.fresh) {  // the run's start
         BatchTrackRec z{};

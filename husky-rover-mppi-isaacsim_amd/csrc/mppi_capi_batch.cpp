@@ -300,7 +300,8 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
       use_proj[vi >= 0 ? b->variants[vi].proj : proj] = true;
     }
     r.steps_run = 0;
-    const bool outside = std::fabs(r.x0 - r.gx) > pol.goal_tol || std::fabs(r.y0 - r.gy) > pol.goal_tol;
+    // (inside on both axes; a NaN coordinate is outside: include/mppi.h)
+    const bool outside = !(std::fabs(r.x0 - r.gx) <= pol.goal_tol && std::fabs(r.y0 - r.gy) <= pol.goal_tol);
     r.active = b->is_set[e] && outside ? 1 : 0;
     if (b->is_set[e] && !outside) r.reached = 1;
     active += r.active;

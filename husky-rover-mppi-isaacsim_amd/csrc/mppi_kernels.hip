@@ -1730,7 +1730,8 @@ __global__ __launch_bounds__(2 * TB) void mppi_rollout_pair_kernel(const Rollout
     cost = cost + a.w_speed * sp;
     cost = cost + a.w_obs * ob;
     if (valid) a.cost_out[kl] = cost;
-    cost_lds[tj] = valid ? cost : INFINITY;
+    // a cost that is not finite (NaN, +inf, -inf) is dead: the leaf sees +inf
+    cost_lds[tj] = (valid && fabsf(cost) < INFINITY) ? cost : INFINITY;
   }
   __syncthreads();
   if constexpr (MODE == 0)  // rows hold the normals; the leaf recomputes the sampled controls
@@ -2133,7 +2134,8 @@ __device__ __forceinline__ int roles_body(const RolloutArgs& a, int blk, unsigne
     cost = cost + a.w_speed * cost_lds[tj];  // (the producer's speed critic sum)
     cost = cost + a.w_obs * c_ob;
     if (valid) a.cost_out[kl] = cost;
-    cost_lds[tj] = valid ? cost : INFINITY;
+    // a cost that is not finite (NaN, +inf, -inf) is dead: the leaf sees +inf
+    cost_lds[tj] = (valid && fabsf(cost) < INFINITY) ? cost : INFINITY;
   }
   __syncthreads();
   if constexpr (MODE == 0)  // rows hold the normals; the leaf recomputes the sampled controls

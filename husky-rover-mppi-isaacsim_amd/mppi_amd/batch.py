@@ -389,11 +389,12 @@ def normalise_heading(hv):
 
 
 def is_active(state, policy=None):
-    """The loop's condition before a step: |x - goal_x| > tol or |y - goal_y| > tol, in float32."""
+    """The loop's condition before a step: not (|x - goal_x| <= tol and |y - goal_y| <= tol), in
+    float32; a NaN coordinate is never inside the tolerance."""
     tol = F32((policy or RUN_POLICY)["goal_tol"])
     x, y = F32(state["x"]), F32(state["y"])
     gx, gy = F32(state["goal_x"]), F32(state["goal_y"])
-    return bool(np.abs(x - gx) > tol or np.abs(y - gy) > tol)
+    return not bool(np.abs(x - gx) <= tol and np.abs(y - gy) <= tol)
 
 
 def advance_state(state, traj0, heading0, v, w, robot_radius, policy=None):

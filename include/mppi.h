@@ -420,7 +420,9 @@ int mppi_get_score_ms(mppi_ctx* ctx, double* ms);
  *   component rounded to float32; ww = (w w) / sigma_div; std_dev_u1 = max(sigma_base, sigma_base -
  *   ww); std_dev_u2 = max(sigma_base, sigma_base + ww); half = (w r) / 2; left_wheel_speed = v -
  *   half; right_wheel_speed = v + half; the goal is unchanged.
- * An episode is active before a step iff |x - goal_x| > goal_tol or |y - goal_y| > goal_tol.
+ * An episode is active before a step unless |x - goal_x| <= goal_tol and |y - goal_y| <= goal_tol (with
+ * finite coordinates: iff |x - goal_x| > goal_tol or |y - goal_y| > goal_tol; a NaN coordinate is
+ * never inside the tolerance, so a pose that is not a number does not count as reached).
  * {0.4, 1, 0.5} is run()'s policy (:763-784), {0.25, 3, 0.5} the Isaac loop's
  * (visual_terrain_stack_full_terrain.py:510-511).  Each step is bitwise the mppi_step of a context
  * with the episode's seed, state and step index. */
@@ -698,7 +700,7 @@ int  mppi_batch_step_device(mppi_batch* b, int32_t proj, const mppi_batch_io* io
  * rollout's lookup: the truncating cell index and the axis-swapped bilinear of projection_warp.py.
  * The row extends the run's score, and with keep_log it goes to the episode's log, where
  * mppi_batch_get_log and mppi_batch_score (origins NULL: the run's start and goal) read the current
- * or most recent run.  Then the goal test !(|x - goal_x| > goal_tol || |y - goal_y| > goal_tol) on
+ * or most recent run.  Then the goal test (|x - goal_x| <= goal_tol && |y - goal_y| <= goal_tol) on
  * the ingested state and the cap decide: the run ends reached, or unreached when its rows reach
  * max_steps.  A start inside the tolerance ends at once with steps 0, reached 1 and a score row of
  * zeros.  A reset that finds an unfinished run with at least one row ends it as abandoned (its state

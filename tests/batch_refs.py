@@ -41,7 +41,8 @@ def start_state(start, goal, heading=(1.0, 0.0, 0.0), s1=0.25, s2=0.25):
 
 def active(st, pol):
     tol = F32(pol["goal_tol"])
-    return bool(np.abs(F32(st["x"] - st["gx"])) > tol or np.abs(F32(st["y"] - st["gy"])) > tol)
+    # inside the tolerance on both axes ends the loop; a NaN coordinate is never inside
+    return not bool(np.abs(F32(st["x"] - st["gx"])) <= tol and np.abs(F32(st["y"] - st["gy"])) <= tol)
 
 
 def rule(st, traj0, hv0, v, w, r, pol):

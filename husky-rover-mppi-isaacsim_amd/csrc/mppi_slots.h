@@ -13,7 +13,11 @@ namespace mppi {
 constexpr int kEpsSlots = 3;
 
 struct EpsPolicy {
-  int64_t step[kEpsSlots] = {-1, -1, -1};          // the Philox step whose normals the slot holds (-1: none)
+  // A step is any uint64_t (the step counter is a full word of the Philox counter and
+  // wraps at 2^64), so no 64-bit value can stand for "none".  The slot keeps the step in a wider signed
+  // word: 0 .. 2^64 - 1 is the step it holds, -1 is none, and no step aliases it.
+  using held_t = __int128;
+  held_t step[kEpsSlots] = {-1, -1, -1};            // the Philox step whose normals the slot holds (-1: none)
   bool pending[kEpsSlots] = {false, false, false};  // its fill is in flight: the slot's event tells when it is done
 
   // The slot that holds `s`, or -1.  (No two slots hold one step: a step is generated only when
@@ -21,27 +25,26 @@ struct EpsPolicy {
   int find(uint64_t s) const {
     int slot = -1;
     for (int i = 0; i < kEpsSlots; ++i)
-      if (step[i] == (int64_t)s) slot = i;
+      if (step[i] == (held_t)s) slot = i;
     return slot;
   }
   bool holds(uint64_t s) const { return find(s) >= 0; }
-  // A slot other than `used` that holds none of the steps in (s, s + 2]: the stalest one (its
-  // last reader is a rollout enqueued before the current one).  -1: none.
+  // A slot other than `used` that holds none of the steps in (s, s + 2], taken modulo 2^64: the
+  // stalest one (its last reader is a rollout enqueued before the current one).  -1: none.
   int victim(int used, uint64_t s) const {
     for (int i = 0; i < kEpsSlots; ++i) {
       if (i == used) continue;
-      const int64_t t = step[i];
-      if (t > (int64_t)s && t <= (int64_t)s + 2) continue;
+      if (step[i] >= 0 && (uint64_t)((uint64_t)step[i] - s - 1) < 2) continue;
       return i;
     }
     return -1;
   }
   void mark_pending(int i, uint64_t s) {  // a fill of step s was enqueued and its event recorded
-    step[i] = (int64_t)s;
+    step[i] = (held_t)s;
     pending[i] = true;
   }
   void mark_ready(int i, uint64_t s) {  // holds s with no event to wait for (ordered by its stream, or by the server)
-    step[i] = (int64_t)s;
+    step[i] = (held_t)s;
     pending[i] = false;
   }
   void settled(int i) { pending[i] = false; }  // the fill's event was waited for

@@ -544,6 +544,16 @@ def check_paths(traj, lin_vel, left_wheel=None, right_wheel=None, lengths=None):
     return n, L, traj, lin_vel, left_wheel, right_wheel, lengths
 
 
+def step_word(step):
+    """The Philox step of a step call as an integer in [0, 2^64) (include/mppi.h mppi_step; DESIGN.md §4
+    D14: the counter is a full 64-bit word and the step after 2^64 - 1 is 0).  ValueError outside: ctypes
+    would reduce it modulo 2^64 without a word, and a caller's -1 would run as step 2^64 - 1."""
+    step = int(step)
+    if not 0 <= step <= 0xFFFFFFFFFFFFFFFF:
+        raise ValueError(f"step must lie in [0, 2^64), got {step}")
+    return step
+
+
 class Engine:
     """One device context of the HIP MPPI engine (thin, allocation-free per step)."""
 
@@ -698,7 +708,7 @@ class Engine:
                     right_wheel_sim=b["right_wheel_sim"].reshape(H, 3).copy())
 
     def step(self, proj="3d", step=0, copy=True):
-        rc = self._step_fn(self.ctx, PROJ[proj], int(step), self._outref)
+        rc = self._step_fn(self.ctx, PROJ[proj], step_word(step), self._outref)
         if rc != MPPI_OK:
             self._c(rc, "mppi_step")
         return self._outputs() if copy else None
@@ -726,7 +736,7 @@ class Engine:
         return int(self.lib.mppi_record_len(self.ctx))
 
     def step_partial(self, record_ptr, proj="3d", step=0):
-        self._c(self.lib.mppi_step_partial(self.ctx, PROJ[proj], int(step), C.c_void_p(int(record_ptr))),
+        self._c(self.lib.mppi_step_partial(self.ctx, PROJ[proj], step_word(step), C.c_void_p(int(record_ptr))),
                 "mppi_step_partial")
 
     def step_finish(self, records_ptr, n, copy=True):
@@ -1594,7 +1604,7 @@ class Group:
 
     def step(self, proj="3d", step=0, copy=True):
         m0 = self.members[0]
-        _check(self.lib, self.lib.mppi_group_step(self.h, PROJ[proj], int(step), C.byref(m0._out)),
+        _check(self.lib, self.lib.mppi_group_step(self.h, PROJ[proj], step_word(step), C.byref(m0._out)),
                "mppi_group_step")
         return m0._outputs() if copy else None
 

@@ -64,7 +64,8 @@ typedef struct mppi_params {
   float w_path, w_slope, w_speed, w_obstacle; /* critics_warp.py:325-329               */
   float collision_threshold, collision_penalty; /* critics_warp.py:251-253 (0.99, 1e5) */
   float horizon;            /* MPPI_isaac.py:440 dt*v_max*H (computed by the caller in float64) */
-  uint64_t seed;            /* Philox key (replaces default_rng(42).integers, MPPI_isaac.py:409,517) */
+  uint64_t seed;            /* Philox key (replaces default_rng(42).integers, MPPI_isaac.py:409,517); all 64
+                               bits are key bits, as all 64 of k_offset + trajectory are counter bits (D14) */
 } mppi_params;
 
 /* Per-step robot / goal state: the values MPPI_step reads from the controller
@@ -229,7 +230,9 @@ int mppi_get_nominal(mppi_ctx* ctx, float* u1, float* u2);
  * sample -> filter -> rollout -> critics -> softmax-weighted update -> optimal
  * filter -> optimal (3D) rollout; outputs copied to host.  `step` is the
  * Philox step counter (noise offset); the new nominal sequence replaces the
- * old one, as reset("sim") + _compute_weighted_sum do (:655-670). */
+ * old one, as reset("sim") + _compute_weighted_sum do (:655-670).  Any uint64_t
+ * is a step: the counter word step * ceil(H/2) + t/2 is taken modulo 2^64 and
+ * the step after 2^64 - 1 is step 0. */
 int mppi_step(mppi_ctx* ctx, int32_t proj, uint64_t step, mppi_outputs* out);
 
 /* Same with caller-supplied sampled controls u1,u2 [K*H] trajectory-major

@@ -31,6 +31,19 @@ int main(int argc, char** argv) {
       printf("mismatch seed %llu n %llu k %llu: %a %a %a %a vs %a %a %a %a\n", (unsigned long long)seed,
              (unsigned long long)nn, (unsigned long long)k, a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]);
   }
+  // the word borders of the counter: (n, k) on both sides of 2^32 and at 2^64 - 1, narrow and wide seeds
+  const uint64_t border[] = {0xFFFFFFFFull, 0x100000000ull, 0xFFFFFFFFFFFFFFFFull};
+  const uint64_t seeds[] = {42ull, 0x100000000ull, 0x9E3779B97F4A7C15ull, 0xFFFFFFFFFFFFFFFFull};
+  for (uint64_t seed : seeds)
+    for (uint64_t nn : border)
+      for (uint64_t k : border) {
+        float a[4], b[4];
+        noise_block(seed, nn, k, a, a + 1, a + 2, a + 3);
+        noise_block_pk(seed, nn, k, b, b + 1, b + 2, b + 3);
+        if (cmp4(a, b) && bad++ < 10)
+          printf("border mismatch seed %llx n %llx k %llx\n", (unsigned long long)seed, (unsigned long long)nn,
+                 (unsigned long long)k);
+      }
   // every edge of the 24-bit uniforms through the Box-Muller pair directly (u = 2^-24 .. 1, v = 0 ..)
   const uint32_t edges[] = {0u, 0xFFu, 0x100u, 0x1FFu, 0x7FFFFF00u, 0x80000000u, 0xFFFFFEFFu, 0xFFFFFF00u, 0xFFFFFFFFu};
   for (uint32_t ra : edges)

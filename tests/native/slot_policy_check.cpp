@@ -23,12 +23,20 @@ static int g_fail = 0;
   } while (0)
 
 // ---- normals slots ----
+// A step is any uint64_t and the counter wraps at 2^64, so "none" is a flag beside
+// the step, never a step value, and every sum or difference of steps below is modulo 2^64.
+struct Held {
+  bool has;
+  uint64_t step;
+};
+
 // The rule as the step engine has always applied it, restated literally: the lowest index other
-// than `used` whose step is not in (s, s + 2], or -1.
-static int victim_rule(const int64_t st[3], int used, int64_t s) {
+// than `used` that holds no step, or a step not in (s, s + 2] (d = step - s - 1 is 0 or 1), or -1.
+static int victim_rule(const Held st[3], int used, uint64_t s) {
   for (int i = 0; i < 3; ++i) {
     if (i == used) continue;
-    const bool keep = st[i] > s && st[i] <= s + 2;
+    const uint64_t d = st[i].step - s - 1u;
+    const bool keep = st[i].has && d < 2u;
     if (!keep) return i;
   }
   return -1;
@@ -36,35 +44,76 @@ static int victim_rule(const int64_t st[3], int used, int64_t s) {
 
 // Linear search; of equal entries (never reachable: a step is generated only when the search
 // misses) the highest index, as the engine's search loop had it.
-static int find_linear(const int64_t st[3], int64_t s) {
+static int find_linear(const Held st[3], uint64_t s) {
   int r = -1;
   for (int i = 0; i < 3; ++i)
-    if (st[i] == s) r = i;
+    if (st[i].has && st[i].step == s) r = i;
   return r;
 }
 
 static void check_eps() {
   static_assert(kEpsSlots == 3, "the enumeration below is over three slots");
-  long states = 0;
-  for (int64_t s : {(int64_t)0, (int64_t)1000}) {
-    const int64_t vals[6] = {-1, s - 1, s, s + 1, s + 2, s + 3};
+  const uint64_t top = ~(uint64_t)0, half = (uint64_t)1 << 63;  // 2^64 - 1, 2^63
+  long states = 0, failed_before = g_fail;
+  for (uint64_t s : {(uint64_t)0, (uint64_t)1000, half - 2, half - 1, half, top - 2, top - 1, top}) {
+    // {none, s - 1, s, s + 1, s + 2, s + 3}; the states are set through the marks alone, as the engine does
+    const Held vals[6] = {{false, 0}, {true, s - 1u}, {true, s}, {true, s + 1u}, {true, s + 2u}, {true, s + 3u}};
     for (int a = 0; a < 6; ++a)
       for (int b = 0; b < 6; ++b)
         for (int c = 0; c < 6; ++c) {
-          const int64_t st[3] = {vals[a], vals[b], vals[c]};
+          const Held st[3] = {vals[a], vals[b], vals[c]};
           EpsPolicy p;
-          for (int i = 0; i < 3; ++i) p.step[i] = st[i];
+          for (int i = 0; i < 3; ++i)
+            if (st[i].has) p.mark_ready(i, st[i].step);
           for (int used = 0; used < 3; ++used) {
-            CHECK(p.victim(used, (uint64_t)s) == victim_rule(st, used, s));
+            CHECK(p.victim(used, s) == victim_rule(st, used, s));
             ++states;
           }
-          for (int64_t q : {s, s + 1, s + 2, s + 3, s + 7}) {
-            CHECK(p.find((uint64_t)q) == find_linear(st, q));
-            CHECK(p.holds((uint64_t)q) == (find_linear(st, q) >= 0));
+          for (uint64_t q : {s - 1u, s, s + 1u, s + 2u, s + 3u, s + 7u}) {
+            CHECK(p.find(q) == find_linear(st, q));
+            CHECK(p.holds(q) == (find_linear(st, q) >= 0));
           }
         }
+    if (g_fail != failed_before) {
+      std::printf("  (%ld checks failed at s = 0x%016llx)\n", (long)(g_fail - failed_before), (unsigned long long)s);
+      failed_before = g_fail;
+    }
   }
-  CHECK(states == 2 * 216 * 3);
+  CHECK(states == 8 * 216 * 3);
+  {  // a fresh policy holds no step at all
+    EpsPolicy f;
+    for (uint64_t q : {(uint64_t)0, (uint64_t)1, half - 1, half, top - 1, top}) CHECK(f.find(q) == -1 && !f.holds(q));
+    for (uint64_t s : {(uint64_t)0, half - 1, top - 2, top - 1, top}) CHECK(f.victim(0, s) == 1 && f.victim(1, s) == 0);
+  }
+  {  // the steps over the wrap, as speculate_eps walks them: two victims for + 1 and + 2, found again
+    EpsPolicy w;
+    const uint64_t s = top - 2;  // 2^64 - 3
+    w.mark_ready(0, s);
+    const int v1 = w.victim(0, s);
+    CHECK(v1 == 1);
+    w.mark_pending(v1, s + 1u);
+    const int v2 = w.victim(0, s);
+    CHECK(v2 == 2);
+    w.mark_pending(v2, s + 2u);  // step 2^64 - 1
+    CHECK(w.find(s) == 0 && w.find(s + 1u) == 1 && w.find(top) == 2 && w.victim(0, s) == -1);
+    // step 2^64 - 2 reads slot 1; step + 2 is step 0, into the slot of the stale 2^64 - 3
+    CHECK(w.holds(top) && !w.holds(0) && w.victim(1, s + 1u) == 0);
+    w.mark_pending(0, s + 3u);
+    CHECK(w.find(0) == 0 && w.victim(1, s + 1u) == -1);
+    // step 2^64 - 1 reads slot 2; step 0 is kept, step 1 goes over the stale 2^64 - 2
+    CHECK(w.holds(0) && !w.holds(1) && w.victim(2, top) == 1);
+    w.mark_pending(1, 1);
+    CHECK(w.find(top) == 2 && w.find(0) == 0 && w.find(1) == 1 && w.victim(2, top) == -1);
+    CHECK(w.victim(0, 0) == 2);  // at step 0, step 2^64 - 1 is stale
+    w.forget_steps();
+    CHECK(w.find(top) == -1 && w.find(0) == -1 && w.find(1) == -1 && !w.holds(top));
+    w.mark_ready(2, top);
+    w.invalidate(2);
+    CHECK(w.find(top) == -1);
+    w.mark_ready(2, top);
+    w.invalidate_all();
+    CHECK(w.find(top) == -1 && w.find(0) == -1);
+  }
   // the marks
   EpsPolicy p;
   CHECK(p.find(0) == -1 && p.victim(0, 0) == 1);

@@ -181,6 +181,64 @@ __device__ __forceinline__ void episode_goal_fields(BatchEpisode* ep, float x, f
   ep->speed_on = (dist < 2.0f) ? 0 : 1;
 }
 
+// The 11-float state of include/mppi.h's mppi_state (heading as given) between two records that carry its
+// names (BatchEpisode, BatchTask, BatchTaskResult), and from the float[11] of an ingest.  Load and store
+// alternate field by field, and the ingest's form reads position and goal first, as the copies were written
+// before there was one statement of them: the kernels' instruction streams follow that order.
+template <class Dst, class Src>
+__device__ __forceinline__ void copy_state(Dst& d, const Src& s) {
+  d.x0 = s.x0;
+  d.y0 = s.y0;
+  d.h0x = s.h0x;
+  d.h0y = s.h0y;
+  d.h0z = s.h0z;
+  d.wl = s.wl;
+  d.wr = s.wr;
+  d.gx = s.gx;
+  d.gy = s.gy;
+  d.s1 = s.s1;
+  d.s2 = s.s2;
+}
+template <class Dst>
+__device__ __forceinline__ void copy_state(Dst& d, const float* s) {
+  const float x = s[0], y = s[1], gx = s[7], gy = s[8];
+  d.x0 = x;
+  d.y0 = y;
+  d.h0x = s[2];
+  d.h0y = s[3];
+  d.h0z = s[4];
+  d.wl = s[5];
+  d.wr = s[6];
+  d.gx = gx;
+  d.gy = gy;
+  d.s1 = s[9];
+  d.s2 = s[10];
+}
+
+// The accumulator of a path that starts at (x, y), into a zeroed record: every chain, pending term and count
+// stay zero; the goal terms of the start are the critics' scalar parts the episode's record has just received.
+__device__ __forceinline__ void score_acc_start(BatchScoreAcc& z, const BatchEpisode* ep, float x, float y) {
+  z.x0 = x;
+  z.y0 = y;
+  z.igx = ep->igx;
+  z.igy = ep->igy;
+  z.pf_scale = ep->pf_scale;
+  z.pf_far = ep->pf_far;
+  z.speed_on = ep->speed_on;
+}
+
+// One row of a log: the pose, the heading h[0..3) and the command.
+__device__ __forceinline__ void log_row(float* lg, float x, float y, float z, const float* h, float v, float w) {
+  lg[0] = x;
+  lg[1] = y;
+  lg[2] = z;
+  lg[3] = h[0];
+  lg[4] = h[1];
+  lg[5] = h[2];
+  lg[6] = v;
+  lg[7] = w;
+}
+
 // The claim rule of the task queue, run by one thread of lane e whose task is over (or that has
 // none yet: the first fill).  Takes the next index of the list with one agent-scope atomic add; a
 // task whose start already passes the goal test takes no step: its result is written at once
@@ -190,12 +248,10 @@ __device__ __forceinline__ void episode_goal_fields(BatchEpisode* ep, float x, f
 // variant index and scene record, which the next step's kernels read.  With the list exhausted the
 // lane goes inactive and leaves the pinned count.  Returns whether a task was loaded (the caller
 // then zeroes the lane's nominal double buffer).
-// SCORED (a scored list): the lane's accumulator record starts over with the claimed task: every
-// chain, pending term and count zero, and the goal terms of the task's start, which are the critics'
-// scalar parts the lane's record has just received.
-template <bool SCORED = false>
+// SCORED (a scored list): the lane's accumulator record *acc starts over with the claimed task.
+template <bool SCORED>
 __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep,
-                                               BatchScoreAcc* acc = nullptr) {
+                                               BatchScoreAcc* acc) {
   for (;;) {
     const int i = __hip_atomic_fetch_add(q.next_task, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (i >= q.n) {
@@ -208,43 +264,17 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
     const float x = t->x0, y = t->y0, gx = t->gx, gy = t->gy;
     if (goal_reached(x, y, gx, gy, b.goal_tol)) {
       BatchTaskResult* r = q.res + i;
-      r->x0 = x;
-      r->y0 = y;
-      r->h0x = t->h0x;
-      r->h0y = t->h0y;
-      r->h0z = t->h0z;
-      r->wl = t->wl;
-      r->wr = t->wr;
-      r->gx = gx;
-      r->gy = gy;
-      r->s1 = t->s1;
-      r->s2 = t->s2;
+      copy_state(*r, *t);
       r->steps = 0;
       r->reached = 1;
       r->flags = 3;
       continue;
     }
-    ep->x0 = x;
-    ep->y0 = y;
-    ep->h0x = t->h0x;
-    ep->h0y = t->h0y;
-    ep->h0z = t->h0z;
-    ep->wl = t->wl;
-    ep->wr = t->wr;
-    ep->gx = gx;
-    ep->gy = gy;
-    ep->s1 = t->s1;
-    ep->s2 = t->s2;
+    copy_state(*ep, *t);
     episode_goal_fields(ep, x, y, gx, gy, b.horizon);
     if constexpr (SCORED) {
       BatchScoreAcc z{};
-      z.x0 = x;
-      z.y0 = y;
-      z.igx = ep->igx;
-      z.igy = ep->igy;
-      z.pf_scale = ep->pf_scale;
-      z.pf_far = ep->pf_far;
-      z.speed_on = ep->speed_on;
+      score_acc_start(z, ep, x, y);
       *acc = z;
     }
     ep->active = 1;
@@ -266,11 +296,12 @@ __device__ __forceinline__ bool campaign_claim(const BatchArgs& b, const BatchCa
 // through LDS, and on a new task every thread zeroes its share of both halves of the lane's nominal
 // double buffer (what mppi_batch_set_episode does with a memset).  Every thread of the workgroup
 // calls this: the branch is uniform, the barrier is not inside it.
-template <bool SCORED = false>
-__device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchCampaign& q, int e, BatchEpisode* ep,
-                                                bool ended, int tid, int nthreads, int* got,
-                                                BatchScoreAcc* acc = nullptr) {
-  if (tid == 0) *got = (ended && campaign_claim<SCORED>(b, q, e, ep, acc)) ? 1 : 0;
+template <class Form>
+__device__ __forceinline__ void campaign_refill(const BatchArgs& b, const Form& form, int e, BatchEpisode* ep,
+                                                bool ended, int tid, int nthreads, int* got) {
+  BatchScoreAcc* acc = nullptr;  // a scored form: the lane's record
+  if constexpr (Form::kScored) acc = form.scored().acc + e;
+  if (tid == 0) *got = (ended && campaign_claim<Form::kScored>(b, form.queue(), e, ep, acc)) ? 1 : 0;
   __syncthreads();
   if (*got) {
     float* u = b.unom + (size_t)e * 4 * b.H;
@@ -288,15 +319,12 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // CAMPAIGN (mppi_batch_run_tasks): the episode is a lane working through the task list `q`.  Its
 // row goes to its task's rows of the log arena, and when the task ends (goal test passed, or the
 // row count reaches the task's cap) the advance lane writes the task's result and the workgroup
-// refills the lane (campaign_refill above) instead of going inactive.  The campaign form is the
-// instantiation with the queue as its own third kernel argument; the plain form takes the two
-// arguments it always took (BatchArgs does not grow).
+// refills the lane (campaign_refill above) instead of going inactive.
 //
 // STEP (mppi_batch_step_device): the plant is the caller's.  Instead of the advance one lane writes
 // the command (v, w) to io.cmd[e], flips the nominal double buffer and counts the step, and the
 // workgroup copies the 4H + 12 outputs to io.plan[e]: no advance rule, no goal test, no log row, no
-// touch of the active count.  The state stays what the ingest kernel (below) wrote.  The io pointers
-// are this form's own third kernel argument, as the queue is the campaign form's.
+// touch of the active count.  The state stays what the ingest kernel (below) wrote.
 //
 // SCORED (a list set by mppi_batch_set_tasks_scored): the campaign form whose advance lane also
 // extends the four critic chains of the log scorer by the row in hand (mppi_score_chain.h: the same
@@ -305,24 +333,25 @@ __device__ __forceinline__ void campaign_refill(const BatchArgs& b, const BatchC
 // scorer admits them only when that row exists: the near path term of row t (the sum runs over
 // t < L - 1) and the slope term of even row s (it needs row s + 1).  The record is loaded at the head,
 // beside lane_steps; only this lane reads or writes it.  With q.log null (keep_log = 0) no row is
-// written: a uniform branch around the eight stores.  The queue, the yardstick and the two tables
-// are this form's third kernel argument (BatchScoredCampaign).
+// written: a uniform branch around the eight stores.
 //
 // TRACKED (mppi_batch_step_tracked): the step form with one more store pair: (v, w) into the
 // episode's tracking record, where the next tracked ingest finds the command its row is paired with.
-// The io block and the records are this form's third kernel argument (BatchTrackedIo).
+//
+// The kernel's third argument is the form (mppi_kernels.h): it names which of the above it is and
+// hands out the queue, the scored block, the io block, the tracking records and the wheel options.
 
 // Row `row` of a path enters the accumulator: (x, y, z) and v, what the log row holds; (gx, gy) the
 // path's goal, cm its costmap.  The one statement of the rule for the scored campaign's advance lane
-// and the tracked ingest.  Y: the block that carries the yardstick (BatchScoredCampaign, BatchTrack).
+// and the tracked ingest; cm (cm_size squared cells) is the context's costmap or the one of the path's slot.
 // WX (the wheel forms), wheels: the slope chain reads the row's wheel contacts cw (left | right) in place of
 // the body waypoint: slope_one on both wheels against the previous even contacts in wa, the larger value
 // (the scorer's WHEELS slope wave; critics_warp.py:168-218), in the same order over the even rows.  (wa and
 // cw go in by reference and the choice as a flag: behind a pointer that may be null they stayed in memory.)
-template <bool WX, class Y>
-__device__ __forceinline__ void score_extend_row_x(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
-                                                   float y, float z, float v, float gx, float gy, bool wheels,
-                                                   BatchWheelAcc& wa, const float (&cw)[6]) {
+template <bool WX>
+__device__ __forceinline__ void score_extend_row_x(BatchScoreAcc& sa, const BatchYardstick& yd, const float* cm,
+                                                   int cm_size, int row, float x, float y, float z, float v, float gx,
+                                                   float gy, bool wheels, BatchWheelAcc& wa, const float (&cw)[6]) {
   if (!sa.pf_far) {  // the near branch: the term of row - 1 enters now that this row exists
     if (row >= 1) sa.path = sa.path + sa.path_pend;
     sa.path_pend = chain::path_near(x, y, gx, gy);
@@ -352,7 +381,7 @@ __device__ __forceinline__ void score_extend_row_x(BatchScoreAcc& sa, const Y& y
     sa.slope = sa.slope + sa.slope_pend;
   }
   if (sa.speed_on) sa.speed = chain::speed(sa.speed, yd.vmax, v);
-  const float c = cm[chain::cm_index(yd.hw, yd.res_c, yd.cm_size, x, y)];
+  const float c = cm[chain::cm_index(yd.hw, yd.res_c, cm_size, x, y)];
   const chain::ObstacleAcc oa = chain::obstacle(sa.obs, sa.col, c, yd.thr, yd.pen);
   sa.obs = oa.acc;
   sa.col = oa.col;
@@ -366,19 +395,19 @@ __device__ __forceinline__ void score_extend_row_x(BatchScoreAcc& sa, const Y& y
     sa.sz = z;
   }
 }
-template <class Y>
-__device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const Y& yd, const float* cm, int row, float x,
-                                                 float y, float z, float v, float gx, float gy) {
+__device__ __forceinline__ void score_extend_row(BatchScoreAcc& sa, const BatchYardstick& yd, const float* cm,
+                                                 int cm_size, int row, float x, float y, float z, float v, float gx,
+                                                 float gy) {
   BatchWheelAcc none{};
   const float no_contacts[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  score_extend_row_x<false>(sa, yd, cm, row, x, y, z, v, gx, gy, false, none, no_contacts);
+  score_extend_row_x<false>(sa, yd, cm, cm_size, row, x, y, z, v, gx, gy, false, none, no_contacts);
 }
 
 // The score row of a path that ended with row `row` at (x, y), into table[index]: L = row + 1 rows; the
 // far branch and the orientation critic read the last ones (sa.lx, sa.ly: row - 1).
-template <class Y, class Index>
-__device__ __forceinline__ void score_write(BatchTaskScore* table, Index index, const BatchScoreAcc& sa, const Y& yd,
-                                            int row, float x, float y, float gx, float gy) {
+template <class Index>
+__device__ __forceinline__ void score_write(BatchTaskScore* table, Index index, const BatchScoreAcc& sa,
+                                            const BatchYardstick& yd, int row, float x, float y, float gx, float gy) {
   const float pf = sa.pf_far ? chain::path_far(x, y, sa.igx, sa.igy, sa.pf_scale) : sa.path;
   const float po = row >= 1 ? chain::orientation(gx, gy, sa.x0, sa.y0, sa.lx, sa.ly, x, y) : 0.0f;
   BatchTaskScore* o = table + index;
@@ -393,55 +422,22 @@ __device__ __forceinline__ void score_write(BatchTaskScore* table, Index index, 
   o->length = sa.length;
 }
 
-__device__ __forceinline__ const BatchCampaign* queue_of() { return nullptr; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchCampaign& q) { return &q; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchIo&) { return nullptr; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchScoredCampaign& s) { return &s.q; }
-__device__ __forceinline__ const BatchIo* io_of() { return nullptr; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchCampaign&) { return nullptr; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchIo& io) { return &io; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchScoredCampaign&) { return nullptr; }
-template <class... Q>
-__device__ __forceinline__ const BatchScoredCampaign* scored_of(const Q&...) { return nullptr; }
-__device__ __forceinline__ const BatchScoredCampaign* scored_of(const BatchScoredCampaign& s) { return &s; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchTrackedIo&) { return nullptr; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchTrackedIo& t) { return &t.io; }
-template <class... Q>
-__device__ __forceinline__ BatchTrackRec* track_of(const Q&...) { return nullptr; }
-__device__ __forceinline__ BatchTrackRec* track_of(const BatchTrackedIo& t) { return t.rec; }
-// the wheel forms: the form's own block, then BatchWheelOpts
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelRun&) { return nullptr; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelCampaign& w) { return &w.q; }
-__device__ __forceinline__ const BatchCampaign* queue_of(const BatchWheelScored& w) { return &w.s.q; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchWheelRun&) { return nullptr; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchWheelCampaign&) { return nullptr; }
-__device__ __forceinline__ const BatchIo* io_of(const BatchWheelScored&) { return nullptr; }
-__device__ __forceinline__ const BatchScoredCampaign* scored_of(const BatchWheelScored& w) { return &w.s; }
-template <class... Q>
-__device__ __forceinline__ const BatchWheelOpts* wheels_of(const Q&...) { return nullptr; }
-__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelRun& w) { return &w.x; }
-__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelCampaign& w) { return &w.x; }
-__device__ __forceinline__ const BatchWheelOpts* wheels_of(const BatchWheelScored& w) { return &w.x; }
-template <class... Queue>
+template <class Form>
 __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const FinishArgs f_in, const BatchArgs b,
-                                                                         const Queue... queue) {
-  static_assert(sizeof...(Queue) <= 1, "at most the one queue, or the one io block");
+                                                                         const Form form) {
   // WX: a wheel form (mppi_batch_set_wheel_log / _set_score_options): the advance lane also reads row 0 of
   // the optimal rollout's wheel contacts (floats 4H + 6 .. 4H + 11 of the finish output), logs them beside
   // the row, extends the slope chain in its wheel form and the path metrics by them
-  constexpr bool WX = ((std::is_same<Queue, BatchWheelRun>::value || std::is_same<Queue, BatchWheelCampaign>::value ||
-                        std::is_same<Queue, BatchWheelScored>::value) || ...);
-  constexpr bool SCORED =
-      ((std::is_same<Queue, BatchScoredCampaign>::value || std::is_same<Queue, BatchWheelScored>::value) || ...);
-  constexpr bool CAMPAIGN =
-      ((std::is_same<Queue, BatchCampaign>::value || std::is_same<Queue, BatchWheelCampaign>::value) || ...) || SCORED;
-  constexpr bool TRACKED = (std::is_same<Queue, BatchTrackedIo>::value || ...);
-  constexpr bool STEP = (std::is_same<Queue, BatchIo>::value || ...) || TRACKED;
-  static_assert(sizeof...(Queue) == (CAMPAIGN || STEP || WX ? 1 : 0),
-                "the third argument is a BatchCampaign, a BatchScoredCampaign, a BatchIo, a BatchTrackedIo or a wheel form");
-  const BatchCampaign* q = queue_of(queue...);
-  const BatchScoredCampaign* sc = scored_of(queue...);
-  const BatchWheelOpts* wx = wheels_of(queue...);
+  constexpr bool WX = Form::kWheels, SCORED = Form::kScored, CAMPAIGN = Form::kCampaign, TRACKED = Form::kTracked,
+                 STEP = Form::kStep;
+  static_assert((!SCORED || CAMPAIGN) && (!TRACKED || STEP) && !(CAMPAIGN && STEP) && !(WX && STEP),
+                "a scored form is a campaign, a tracked form a step; a step neither runs a queue nor logs wheels");
+  const BatchCampaign* q = nullptr;
+  const BatchScoredCampaign* sc = nullptr;
+  const BatchWheelOpts* wx = nullptr;
+  if constexpr (CAMPAIGN) q = &form.queue();
+  if constexpr (SCORED) sc = &form.scored();
+  if constexpr (WX) wx = &form.wheels();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
@@ -545,7 +541,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
   if constexpr (STEP) {
     // ---------------- (3') the command and the plan out (after finish_phase2's closing barrier; its
     // outputs were written through, so agent-scope loads see them)
-    const BatchIo* io = io_of(queue...);
+    const BatchIo* io = &form.io();
     auto ld = [&](int i) __attribute__((always_inline)) {
       return __hip_atomic_load(f.out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
@@ -560,7 +556,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
         io->cmd[2 * (size_t)e + 1] = ld(3 * H);
       }
       if constexpr (TRACKED) {  // the command the episode's next row is paired with
-        BatchTrackRec* tr = track_of(queue...) + e;
+        BatchTrackRec* tr = form.track() + e;
         tr->v = ld(2 * H);
         tr->w = ld(3 * H);
       }
@@ -586,28 +582,22 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     const double d0 = (double)ld(4 * H + 3), d1 = (double)ld(4 * H + 4), d2 = (double)ld(4 * H + 5);
     const double nn = __builtin_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
     const float hx = (float)(d0 / nn), hy = (float)(d1 / nn), hz = (float)(d2 / nn);
-    bool log_row = row < (CAMPAIGN ? ln.max_steps : b.log_cap);
-    if constexpr (SCORED) log_row = log_row && q->log != nullptr;
+    bool logs = row < (CAMPAIGN ? ln.max_steps : b.log_cap);
+    if constexpr (SCORED) logs = logs && q->log != nullptr;
     float cw[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // WX: left_wheel_sim[0] | right_wheel_sim[0]
     if constexpr (WX) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) cw[i] = ld(4 * H + 6 + i);
-      if (log_row && wx->wlog) {  // the row of the same index in the parallel array
+      if (logs && wx->wlog) {  // the row of the same index in the parallel array
         float* wl = wx->wlog + (CAMPAIGN ? (size_t)ln.log_base + row : (size_t)e * b.log_cap + row) * 6;
 #pragma unroll
         for (int i = 0; i < 6; ++i) wl[i] = cw[i];
       }
     }
-    if (log_row) {
-      float* lg = CAMPAIGN ? q->log + ((size_t)ln.log_base + row) * 8 : b.log + ((size_t)e * b.log_cap + row) * 8;
-      lg[0] = x;
-      lg[1] = y;
-      lg[2] = z;
-      lg[3] = hx;
-      lg[4] = hy;
-      lg[5] = hz;
-      lg[6] = v;
-      lg[7] = w;
+    if (logs) {
+      const float h[3] = {hx, hy, hz};
+      log_row(CAMPAIGN ? q->log + ((size_t)ln.log_base + row) * 8 : b.log + ((size_t)e * b.log_cap + row) * 8, x, y, z,
+              h, v, w);
     }
     const float ww = (w * w) / sigma_div;
     const float half = (w * b.rwheel) / 2.0f;
@@ -627,16 +617,18 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
     const bool reached = goal_reached(x, y, gx, gy, b.goal_tol);
     // row `row` of the task's path enters the chains: (x, y, z) and v, what the log row holds
     if constexpr (SCORED && WX) {
-      score_extend_row_x<true>(sa, *sc, cm, row, x, y, z, v, gx, gy, wx->wacc != nullptr, wa, cw);
+      score_extend_row_x<true>(sa, sc->y, cm, sc->cm_size, row, x, y, z, v, gx, gy, wx->wacc != nullptr, wa, cw);
       if (wx->macc) metrics_row(ma, row, x, y, z);
     } else if constexpr (SCORED) {
-      score_extend_row(sa, *sc, cm, row, x, y, z, v, gx, gy);
+      score_extend_row(sa, sc->y, cm, sc->cm_size, row, x, y, z, v, gx, gy);
     }
     if constexpr (CAMPAIGN) {
       q->lane_steps[e] = lane_steps + 1;
       ended = reached || row + 1 >= ln.max_steps;
       if (ended) {
         BatchTaskResult* r = q->res + ln.task;
+        // (the state the episode has just received and its goal, from the values in hand: a record built
+        // for copy_state, or a read back from *ep, changes the kernel's instruction stream)
         r->x0 = x;
         r->y0 = y;
         r->h0x = hx;
@@ -654,7 +646,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
       }
       if constexpr (SCORED) {
         if (ended) {
-          score_write(sc->score, ln.task, sa, *sc, row, x, y, gx, gy);
+          score_write(sc->score, ln.task, sa, sc->y, row, x, y, gx, gy);
           if constexpr (WX)
             if (wx->macc) wx->metrics[ln.task] = ma.m;
         } else {  // (the claim resets the record of a lane whose task ended)
@@ -673,24 +665,16 @@ __global__ __launch_bounds__(FIN_THREADS) void mppi_batch_finish_kernel(const Fi
       __hip_atomic_fetch_add(b.active_count, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-  if constexpr (SCORED)
-    campaign_refill<true>(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw), sc->acc + e);
-  else if constexpr (CAMPAIGN)
-    campaign_refill(b, *q, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw));
+  if constexpr (CAMPAIGN) campaign_refill(b, form, e, ep, ended, tid, FIN_THREADS, reinterpret_cast<int*>(smem_raw));
 }
 
-// The first fill of a campaign: every lane claims as a finishing lane does.  Grid E, one wave each.
-__global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b, const BatchCampaign q) {
+// The first fill of a campaign: every lane claims as a finishing lane does (a scored list's claim also
+// resets the lane's accumulator record).  Grid E, one wave each.
+template <class Form>
+__global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b, const Form form) {
   __shared__ int got;
   const int e = blockIdx.x;
-  campaign_refill(b, q, e, b.ep + e, true, (int)threadIdx.x, 64, &got);
-}
-
-// The first fill of a scored list: the claim that also resets the lane's accumulator record.
-__global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b, const BatchScoredCampaign s) {
-  __shared__ int got;
-  const int e = blockIdx.x;
-  campaign_refill<true>(b, s.q, e, b.ep + e, true, (int)threadIdx.x, 64, &got, s.acc + e);
+  campaign_refill(b, form, e, b.ep + e, true, (int)threadIdx.x, 64, &got);
 }
 
 // The way into the episode record for a plant that lives on the device (mppi_batch_step_device):
@@ -702,8 +686,7 @@ __global__ __launch_bounds__(64) void mppi_batch_claim_kernel(const BatchArgs b,
 // An episode that does not step keeps its whole record but `active`, which every launch of the
 // step reads.  Grid E, one wave each; e is the workgroup's, so every read is wave-uniform.  No LDS, no
 // waits: the noise and rollout kernels read the record behind the kernel boundary.
-__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
-                                                                const int* __restrict__ is_set) {
+__device__ __forceinline__ void plain_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set) {
   const int e = blockIdx.x;
   BatchEpisode* ep = b.ep + e;
   const bool on = is_set[e] != 0 && (!io.mask || io.mask[e] != 0);
@@ -713,17 +696,7 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
     if (on) {
       const float* s = io.states + (size_t)e * 11;
       const float x = s[0], y = s[1], gx = s[7], gy = s[8];
-      ep->x0 = x;
-      ep->y0 = y;
-      ep->h0x = s[2];
-      ep->h0y = s[3];
-      ep->h0z = s[4];
-      ep->wl = s[5];
-      ep->wr = s[6];
-      ep->gx = gx;
-      ep->gy = gy;
-      ep->s1 = s[9];
-      ep->s2 = s[10];
+      copy_state(*ep, s);
       episode_goal_fields(ep, x, y, gx, gy, b.horizon);
       ep->reached = 0;
       if (reset) {
@@ -741,6 +714,8 @@ __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b
 
 // The result row of a run that ended: the state of the ending ingest (11 floats in mppi_state order),
 // its rows, the goal test's answer and the status.  The score row is the caller's.
+// (Field by field in the record's order: s is device memory that the kernel has written around, and the
+// ingests' copy_state, which reads position and goal first, gives the tracked ingests another stream.)
 __device__ __forceinline__ void run_result(BatchTaskResult* r, const float* s, int steps, int reached, int status) {
   r->x0 = s[0];
   r->y0 = s[1];
@@ -777,7 +752,7 @@ __device__ __forceinline__ void run_result(BatchTaskResult* r, const float* s, i
 // depends on (e, run count) only: no atomic, and the active count is not touched.  One costmap gather
 // per row, and four DEM loads when z is null; no LDS, no waits.
 //
-// WX (mppi_batch_ingest_kernel's BatchWheelTrack overload; mppi_batch_set_wheel_log / _set_score_options
+// WX (the BatchWheelTrack form; mppi_batch_set_wheel_log / _set_score_options
 // before tracking was set): the row also gets its wheel contacts, formed from the ingested pose by the
 // rollout's own rule (wheel_contacts below) on the episode's DEM; they go to the wheel log beside the row,
 // into the slope chain's wheel form and, with (x, y, z), into the path metrics, whose row is written
@@ -839,7 +814,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
           run_result(&o->r, last, r.rows, 0, kRunAbandoned);
           r.acc.lx = r.px;
           r.acc.ly = r.py;
-          score_write(&o->s, 0, r.acc, t, r.rows - 1, last[0], last[1], r.gx, r.gy);
+          score_write(&o->s, 0, r.acc, t.y, r.rows - 1, last[0], last[1], r.gx, r.gy);
           if constexpr (WX)
             if (wx->macc) wx->metrics[(size_t)e * t.runs_per_episode + runs] = wx->macc[e].m;
         }
@@ -847,17 +822,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
       }
       const float* s = io.states + (size_t)e * 11;
       const float x = s[0], y = s[1], gx = s[7], gy = s[8];
-      ep->x0 = x;
-      ep->y0 = y;
-      ep->h0x = s[2];
-      ep->h0y = s[3];
-      ep->h0z = s[4];
-      ep->wl = s[5];
-      ep->wr = s[6];
-      ep->gx = gx;
-      ep->gy = gy;
-      ep->s1 = s[9];
-      ep->s2 = s[10];
+      copy_state(*ep, s);
       episode_goal_fields(ep, x, y, gx, gy, b.horizon);
       if (reset) {
         ep->cur = 0;
@@ -868,13 +833,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
       BatchRunResult* o = runs < t.runs_per_episode ? t.results + (size_t)e * t.runs_per_episode + runs : nullptr;
       if (reset || r.fresh) {  // the run's start
         BatchTrackRec z{};
-        z.acc.x0 = x;
-        z.acc.y0 = y;
-        z.acc.igx = ep->igx;
-        z.acc.igy = ep->igy;
-        z.acc.pf_scale = ep->pf_scale;
-        z.acc.pf_far = ep->pf_far;
-        z.acc.speed_on = ep->speed_on;
+        score_acc_start(z.acc, ep, x, y);
         z.gx = gx;
         z.gy = gy;
         r = z;
@@ -903,17 +862,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
           z = bilinear<false>(x, y, q, d.rr<false>(), unused);
         }
         if (t.keep_log) {
-          if (row < b.log_cap) {
-            float* lg = b.log + ((size_t)e * b.log_cap + row) * 8;
-            lg[0] = x;
-            lg[1] = y;
-            lg[2] = z;
-            lg[3] = s[2];
-            lg[4] = s[3];
-            lg[5] = s[4];
-            lg[6] = r.v;
-            lg[7] = r.w;
-          }
+          if (row < b.log_cap) log_row(b.log + ((size_t)e * b.log_cap + row) * 8, x, y, z, s + 2, r.v, r.w);
           ep->steps_run = min(row + 1, b.log_cap);
         }
         if constexpr (WX) {
@@ -931,7 +880,7 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
           }
           BatchWheelAcc wa{};
           if (wx->wacc) wa = wx->wacc[e];
-          score_extend_row_x<true>(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy, wx->wacc != nullptr, wa, cw);
+          score_extend_row_x<true>(r.acc, t.y, cm, t.cm_size, row, x, y, z, r.v, r.gx, r.gy, wx->wacc != nullptr, wa, cw);
           if (wx->wacc) wx->wacc[e] = wa;
           if (wx->macc) {
             PathMetricsAcc ma = wx->macc[e];
@@ -939,13 +888,13 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
             wx->macc[e] = ma;
           }
         } else {
-          score_extend_row(r.acc, t, cm, row, x, y, z, r.v, r.gx, r.gy);
+          score_extend_row(r.acc, t.y, cm, t.cm_size, row, x, y, z, r.v, r.gx, r.gy);
         }
         r.rows = row + 1;
         if (reached || row + 1 >= t.max_steps) {
           if (o) {
             run_result(&o->r, s, row + 1, reached ? 1 : 0, reached ? kRunReached : kRunCap);
-            score_write(&o->s, 0, r.acc, t, row, x, y, r.gx, r.gy);
+            score_write(&o->s, 0, r.acc, t.y, row, x, y, r.gx, r.gy);
             if constexpr (WX)
               if (wx->macc) wx->metrics[(size_t)e * t.runs_per_episode + runs] = wx->macc[e].m;
           }
@@ -972,14 +921,13 @@ __device__ __forceinline__ void tracked_ingest(const BatchArgs& b, const BatchIo
   }
 }
 
+// The ingest of the form: plain, tracked, or tracked with the wheel options.
+template <class Form>
 __global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
-                                                                const int* __restrict__ is_set, const BatchTrack t) {
-  tracked_ingest<false>(b, io, is_set, t, nullptr);
-}
-
-__global__ __launch_bounds__(64) void mppi_batch_ingest_kernel(const BatchArgs b, const BatchIo io,
-                                                                const int* __restrict__ is_set, const BatchWheelTrack w) {
-  tracked_ingest<true>(b, io, is_set, w.t, &w.x);
+                                                                const int* __restrict__ is_set, const Form form) {
+  if constexpr (!Form::kTracked) plain_ingest(b, io, is_set);
+  else if constexpr (Form::kWheels) tracked_ingest<true>(b, io, is_set, form.track(), &form.wheels());
+  else tracked_ingest<false>(b, io, is_set, form.track(), nullptr);
 }
 
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st, const BatchNoisePlan& np) {
@@ -1007,85 +955,39 @@ hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t
   return hipGetLastError();
 }
 
-hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b);
+template <class Form>
+hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, const Form& form, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_finish_kernel<Form>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, form);
   return hipGetLastError();
 }
-
-hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st) {
-  void (*k)(const BatchArgs, const BatchIo, const int*) = mppi_batch_ingest_kernel;  // (the tracked form is an overload)
-  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set);
+template <class Form>
+hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, const Form& form,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_ingest_kernel<Form>, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set, form);
   return hipGetLastError();
 }
-
-hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
-                                    hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchIo>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, io);
+template <class Form>
+hipError_t launch_batch_claim(const BatchArgs& b, const Form& form, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_batch_claim_kernel<Form>, dim3((unsigned)b.E), dim3(64), 0, st, b, form);
   return hipGetLastError();
 }
-
-hipError_t launch_batch_ingest_tracked(const BatchArgs& b, const BatchIo& io, const int* is_set, const BatchTrack& t,
-                                       hipStream_t st) {
-  void (*k)(const BatchArgs, const BatchIo, const int*, const BatchTrack) = mppi_batch_ingest_kernel;
-  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set, t);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_step_tracked(const FinishArgs& f, const BatchArgs& b, const BatchTrackedIo& io,
-                                            size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchTrackedIo>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b,
-                     io);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st) {
-  void (*k)(const BatchArgs, const BatchCampaign) = mppi_batch_claim_kernel;  // (the scored list's claim is an overload)
-  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, q);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
-                                        hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, q);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_claim_scored(const BatchArgs& b, const BatchScoredCampaign& s, hipStream_t st) {
-  void (*k)(const BatchArgs, const BatchScoredCampaign) = mppi_batch_claim_kernel;
-  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, s);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_scored(const FinishArgs& f, const BatchArgs& b, const BatchScoredCampaign& s,
-                                      size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchScoredCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f,
-                     b, s);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelRun& w, size_t lds,
-                                      hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelRun>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b, w);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_campaign_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelCampaign& w,
-                                               size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelCampaign>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f,
-                     b, w);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_finish_scored_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelScored& w,
-                                             size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(mppi_batch_finish_kernel<BatchWheelScored>, dim3((unsigned)b.E), dim3(FIN_THREADS), lds, st, f, b,
-                     w);
-  return hipGetLastError();
-}
-
-hipError_t launch_batch_ingest_tracked_wheels(const BatchArgs& b, const BatchIo& io, const int* is_set,
-                                              const BatchWheelTrack& t, hipStream_t st) {
-  void (*k)(const BatchArgs, const BatchIo, const int*, const BatchWheelTrack) = mppi_batch_ingest_kernel;
-  hipLaunchKernelGGL(k, dim3((unsigned)b.E), dim3(64), 0, st, b, io, is_set, t);
-  return hipGetLastError();
-}
+// The forms that exist (a new one: its struct in mppi_kernels.h and its line here).
+#define MPPI_FINISH_FORM(Form) \
+  template hipError_t launch_batch_finish<Form>(const FinishArgs&, const BatchArgs&, const Form&, size_t, hipStream_t)
+MPPI_FINISH_FORM(BatchPlainRun);
+MPPI_FINISH_FORM(BatchIo);
+MPPI_FINISH_FORM(BatchTrackedIo);
+MPPI_FINISH_FORM(BatchCampaign);
+MPPI_FINISH_FORM(BatchScoredCampaign);
+MPPI_FINISH_FORM(BatchWheelRun);
+MPPI_FINISH_FORM(BatchWheelCampaign);
+MPPI_FINISH_FORM(BatchWheelScored);
+#undef MPPI_FINISH_FORM
+#define MPPI_INGEST_FORM(Form) \
+  template hipError_t launch_batch_ingest<Form>(const BatchArgs&, const BatchIo&, const int*, const Form&, hipStream_t)
+MPPI_INGEST_FORM(BatchPlainRun);
+MPPI_INGEST_FORM(BatchTrack);
+MPPI_INGEST_FORM(BatchWheelTrack);
+#undef MPPI_INGEST_FORM
+template hipError_t launch_batch_claim<BatchCampaign>(const BatchArgs&, const BatchCampaign&, hipStream_t);
+template hipError_t launch_batch_claim<BatchScoredCampaign>(const BatchArgs&, const BatchScoredCampaign&, hipStream_t);

@@ -74,11 +74,10 @@ struct mppi_batch {
   DeviceBuf<float> tlog;             // the log arena, [sum of max_steps][8]
   std::vector<int> lane_steps;       // [E] as last read
   enum Campaign { kNotStarted, kUnfinished, kComplete } campaign = kNotStarted;
-  // a scored list (mppi_batch_set_tasks_scored): the yardstick as taken when the list was set (the
-  // pointers and the costmap geometry are filled in by each run), the lanes' accumulator records and
-  // the tasks' score rows
+  // a scored list (mppi_batch_set_tasks_scored): the yardstick as taken when the list was set (each run
+  // takes the costmap as it stands then), the lanes' accumulator records and the tasks' score rows
   bool scored = false;
-  BatchScoredCampaign yard{};
+  BatchYardstick yard{};
   DeviceBuf<BatchScoreAcc> d_acc;     // [E]
   DeviceBuf<BatchTaskScore> d_score;  // [N]
   // tracked device steps (mppi_batch_set_tracking): the yardstick and the caps as taken when tracking
@@ -281,6 +280,79 @@ BatchArgs batch_args(mppi_batch* b, int proj, const mppi_loop_policy& pol) {
   return z;
 }
 
+// The scorer's yardstick: the caller's row where one is given, else the context's parameters; the
+// geometry of the context's costmap and its orientation weight as they stand now.
+BatchYardstick resolve_yardstick(const mppi_ctx* c, const mppi_batch_variant* yardstick) {
+  const mppi_params& p = c->p;
+  BatchYardstick y{};
+  y.hw = c->cmap.hw;
+  y.res_c = c->cmap.res;
+  y.vmax = p.v_max_linear;
+  y.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
+  y.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
+  y.w_path = yardstick ? yardstick->w_path : p.w_path;
+  y.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
+  y.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
+  y.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
+  y.w_orient = c->crit.w_orientation;
+  return y;
+}
+// A yardstick taken earlier, on the costmap as it stands now (a list's at each run, tracking's at each step).
+BatchYardstick on_costmap(BatchYardstick y, const mppi_ctx* c) {
+  y.hw = c->cmap.hw;
+  y.res_c = c->cmap.res;
+  return y;
+}
+
+// The wheel options of a form: each table where `t` turns it on (wlog; wacc; macc and metrics), else null.
+BatchWheelOpts wheel_opts(const mppi_batch* b, const WheelTables& t, float* wlog, BatchWheelAcc* wacc,
+                          PathMetricsAcc* macc, PathMetrics* metrics) {
+  BatchWheelOpts x{};
+  x.wlog = t.wlog ? wlog : nullptr;
+  x.wacc = t.wacc ? wacc : nullptr;
+  x.macc = t.metrics ? macc : nullptr;
+  x.metrics = t.metrics ? metrics : nullptr;
+  x.off = b->c->p.wheel_offset;
+  return x;
+}
+
+// One step of the batch on the context's stream: the noise, one rollout launch per projection in use (a
+// workgroup of the other projection's episode returns at once; without variants that is the run's
+// projection alone), and the finish in the form given.
+template <class Form>
+int enqueue_step(mppi_batch* b, const RolloutArgs& a, const FinishArgs& f, const BatchArgs& z, const Plan& pl,
+                 const bool* use_proj, const Form& finish) {
+  mppi_ctx* c = b->c;
+  HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
+  for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
+    if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
+  HIP_TRY(launch_batch_finish(f, z, finish, pl.fin_lds_bytes, c->stream));
+  return MPPI_OK;
+}
+
+// Up to n_steps steps while an episode is active, the host reading the pinned count every
+// pol.check_every steps; then last_ms takes the stream time since ev[0], which the caller recorded
+// ahead of whatever else it times.
+template <class Form>
+int run_steps(mppi_batch* b, const RolloutArgs& a, const FinishArgs& f, const BatchArgs& z, const Plan& pl,
+              const bool* use_proj, const Form& finish, int n_steps, const mppi_loop_policy& pol) {
+  mppi_ctx* c = b->c;
+  const int every = pol.check_every > 0 ? pol.check_every : 16;
+  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
+    const int m = std::min(every, n_steps - done);
+    for (int i = 0; i < m; ++i)
+      if (int rc = enqueue_step(b, a, f, z, pl, use_proj, finish)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    done += m;
+  }
+  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
+  HIP_TRY(hipEventSynchronize(b->ev[1]));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+  b->last_ms = ms;
+  return MPPI_OK;
+}
+
 int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol) {
   mppi_ctx* c = b->c;
   const Plan pl = make_plan(c);
@@ -337,32 +409,13 @@ int batch_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& pol)
   z.log = b->log;
   z.log_cap = b->log_cap;
   z.scene = b->book.need_table() ? b->d_tab.get() : nullptr;  // null: the kernels of the batch without scenes
-  BatchWheelRun wr{};  // the wheel log on: the finish form that also stores the contacts
-  wr.x.wlog = b->wlog;
-  const int every = pol.check_every > 0 ? pol.check_every : 16;
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
-  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
-    const int m = std::min(every, n_steps - done);
-    for (int i = 0; i < m; ++i) {
-      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
-      // one rollout launch per projection in use (a workgroup of the other projection's episode
-      // returns at once); without variants that is the run's projection alone
-      for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
-        if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-      if (b->wbook.log_wheels())
-        HIP_TRY(launch_batch_finish_wheels(f, z, wr, pl.fin_lds_bytes, c->stream));
-      else
-        HIP_TRY(launch_batch_finish(f, z, pl.fin_lds_bytes, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    done += m;
+  if (b->wbook.log_wheels()) {  // the wheel log on: the finish form that also stores the contacts
+    BatchWheelRun wr{};
+    wr.x.wlog = b->wlog;
+    return run_steps(b, a, f, z, pl, use_proj, wr, n_steps, pol);
   }
-  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
-  HIP_TRY(hipEventSynchronize(b->ev[1]));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
-  b->last_ms = ms;
-  return MPPI_OK;
+  return run_steps(b, a, f, z, pl, use_proj, BatchPlainRun{}, n_steps, pol);
 }
 
 // One step of the set episodes from states in device memory: ingest, noise, a rollout per projection
@@ -400,48 +453,35 @@ int batch_step_device(mppi_batch* b, int proj, const mppi_batch_io& io_in, bool 
   io.cmd = io_in.cmd;
   io.plan = io_in.plan;
   b->unwaited = true;
-  if (tracked) {  // the records, the tables and the scene of this step around the yardstick as taken
-    BatchTrack t = b->trk;
-    t.rec = b->d_track;
-    t.runs = b->d_runs;
-    t.results = b->d_runres;
-    t.z = z_dev;
-    t.done = done_dev;
-    t.cm = c->cmap.cm;
-    t.cm_size = c->cmap.size;
-    t.hw = c->cmap.hw;
-    t.res_c = c->cmap.res;
-    t.Z = c->dem.Z;
-    t.rows = c->dem.rows;
-    t.grid = c->dem.cols;
-    t.x_min = c->dem.x_min;
-    t.y_min = c->dem.y_min;
-    t.res = c->dem.res;
-    z.goal_tol = b->trk_goal_tol;
-    const WheelTables& wt = b->wbook.tracking();
-    if (wt.any()) {
-      BatchWheelTrack w{};
-      w.t = t;
-      w.x.wlog = wt.wlog ? b->wlog.get() : nullptr;
-      w.x.wacc = wt.wacc ? b->d_twacc.get() : nullptr;
-      w.x.macc = wt.metrics ? b->d_tmacc.get() : nullptr;
-      w.x.metrics = wt.metrics ? b->d_runmetrics.get() : nullptr;
-      w.x.off = c->p.wheel_offset;
-      HIP_TRY(launch_batch_ingest_tracked_wheels(z, io, b->d_set, w, c->stream));
-    } else {
-      HIP_TRY(launch_batch_ingest_tracked(z, io, b->d_set, t, c->stream));
-    }
-  } else {
-    HIP_TRY(launch_batch_ingest(z, io, b->d_set, c->stream));
+  if (!tracked) {
+    HIP_TRY(launch_batch_ingest(z, io, b->d_set, BatchPlainRun{}, c->stream));
+    return enqueue_step(b, a, f, z, pl, use_proj, io);
   }
-  HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
-  for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
-    if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-  if (tracked)
-    HIP_TRY(launch_batch_finish_step_tracked(f, z, BatchTrackedIo{io, b->d_track}, pl.fin_lds_bytes, c->stream));
-  else
-    HIP_TRY(launch_batch_finish_step(f, z, io, pl.fin_lds_bytes, c->stream));
-  return MPPI_OK;
+  // the records, the tables and the scene of this step around the caps and the yardstick as taken
+  BatchTrack t = b->trk;
+  t.rec = b->d_track;
+  t.runs = b->d_runs;
+  t.results = b->d_runres;
+  t.z = z_dev;
+  t.done = done_dev;
+  t.cm = c->cmap.cm;
+  t.cm_size = c->cmap.size;
+  t.y = on_costmap(t.y, c);
+  t.Z = c->dem.Z;
+  t.rows = c->dem.rows;
+  t.grid = c->dem.cols;
+  t.x_min = c->dem.x_min;
+  t.y_min = c->dem.y_min;
+  t.res = c->dem.res;
+  z.goal_tol = b->trk_goal_tol;
+  const WheelTables& wt = b->wbook.tracking();
+  if (wt.any()) {
+    const BatchWheelTrack w{t, wheel_opts(b, wt, b->wlog, b->d_twacc, b->d_tmacc, b->d_runmetrics)};
+    HIP_TRY(launch_batch_ingest(z, io, b->d_set, w, c->stream));
+  } else {
+    HIP_TRY(launch_batch_ingest(z, io, b->d_set, t, c->stream));
+  }
+  return enqueue_step(b, a, f, z, pl, use_proj, BatchTrackedIo{io, b->d_track});
 }
 
 // The own-model runs and the task queue write the log, steps_last_run and the episode records that a
@@ -583,26 +623,11 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
   b->tbook.projections(vproj, proj, use_proj);
   const BatchCampaign q = campaign_args(b);
   const size_t E = (size_t)b->E;
-  // a scored list: the yardstick of the list, the queue, the tables and the costmap of this run
-  BatchScoredCampaign sq = b->yard;
-  sq.q = q;
-  sq.acc = b->d_acc;
-  sq.score = b->d_score;
-  sq.cm = c->cmap.cm;
-  sq.cm_size = c->cmap.size;
-  sq.hw = c->cmap.hw;
-  sq.res_c = c->cmap.res;
+  // a scored list: the queue, the tables and the yardstick of the list on the costmap of this run
+  const BatchScoredCampaign sq{q, b->d_acc, b->d_score, c->cmap.cm, c->cmap.size, on_costmap(b->yard, c)};
   // a list set with the wheel log, the wheel slope mode or the metrics on: the wheel forms of the finish
   const WheelTables& lt = b->wbook.list();
-  const bool wheel_form = lt.any();
-  BatchWheelOpts wx{};
-  wx.wlog = lt.wlog ? b->twlog.get() : nullptr;
-  wx.wacc = lt.wacc ? b->d_wacc.get() : nullptr;
-  wx.macc = lt.metrics ? b->d_macc.get() : nullptr;
-  wx.metrics = lt.metrics ? b->d_metrics.get() : nullptr;
-  wx.off = c->p.wheel_offset;
-  const BatchWheelCampaign wq{q, wx};
-  const BatchWheelScored wsq{sq, wx};
+  const BatchWheelOpts wx = wheel_opts(b, lt, b->twlog, b->d_wacc, b->d_macc, b->d_metrics);
   HIP_TRY(hipEventRecord(b->ev[0], c->stream));
   if (b->campaign == mppi_batch::kNotStarted) {
     // the first fill: every lane empty and counted active, then one claim each
@@ -621,38 +646,20 @@ int campaign_run(mppi_batch* b, int proj, int n_steps, const mppi_loop_policy& p
         HIP_TRY(hipMemsetAsync(b->d_macc, 0, E * sizeof(PathMetricsAcc), c->stream));
         HIP_TRY(hipMemsetAsync(b->d_metrics, 0, (size_t)N * sizeof(PathMetrics), c->stream));
       }
-      HIP_TRY(launch_batch_claim_scored(z, sq, c->stream));
+      HIP_TRY(launch_batch_claim(z, sq, c->stream));
     } else {
       HIP_TRY(launch_batch_claim(z, q, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   const int before = *std::max_element(b->lane_steps.begin(), b->lane_steps.end());
-  const int every = pol.check_every > 0 ? pol.check_every : 16;
-  for (int done = 0; done < n_steps && __atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) > 0;) {
-    const int m = std::min(every, n_steps - done);
-    for (int i = 0; i < m; ++i) {
-      HIP_TRY(launch_batch_noise(z, c->p.k_offset, c->stream, noise_plan(b)));
-      for (int pj = MPPI_PROJ_2D; pj <= MPPI_PROJ_3D; ++pj)
-        if (use_proj[pj]) HIP_TRY(launch_batch_rollout(a, z, pl.lds_bytes, c->stream, pj));
-      if (wheel_form && b->scored)
-        HIP_TRY(launch_batch_finish_scored_wheels(f, z, wsq, pl.fin_lds_bytes, c->stream));
-      else if (wheel_form)
-        HIP_TRY(launch_batch_finish_campaign_wheels(f, z, wq, pl.fin_lds_bytes, c->stream));
-      else if (b->scored)
-        HIP_TRY(launch_batch_finish_scored(f, z, sq, pl.fin_lds_bytes, c->stream));
-      else
-        HIP_TRY(launch_batch_finish_campaign(f, z, q, pl.fin_lds_bytes, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    done += m;
-  }
-  HIP_TRY(hipEventRecord(b->ev[1], c->stream));
-  HIP_TRY(hipEventSynchronize(b->ev[1]));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
-  b->last_ms = ms;
-  if (int rc = campaign_pull(b)) return rc;
+  int rc;
+  if (lt.any() && b->scored) rc = run_steps(b, a, f, z, pl, use_proj, BatchWheelScored{sq, wx}, n_steps, pol);
+  else if (lt.any()) rc = run_steps(b, a, f, z, pl, use_proj, BatchWheelCampaign{q, wx}, n_steps, pol);
+  else if (b->scored) rc = run_steps(b, a, f, z, pl, use_proj, sq, n_steps, pol);
+  else rc = run_steps(b, a, f, z, pl, use_proj, q, n_steps, pol);
+  if (rc) return rc;
+  if ((rc = campaign_pull(b))) return rc;
   report((int64_t)*std::max_element(b->lane_steps.begin(), b->lane_steps.end()) - before);
   if (__atomic_load_n(b->active_count.get(), __ATOMIC_ACQUIRE) <= 0) {
     b->campaign = mppi_batch::kComplete;
@@ -668,7 +675,6 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
                int stride, const mppi_batch_variant* yardstick, mppi_path_scores* out, int32_t* rows,
                const char* who, const float* wlog = nullptr, mppi_path_metrics* metrics = nullptr) {
   mppi_ctx* c = b->c;
-  const mppi_params& p = c->p;
   const size_t E = goals.size();
   // one allocation, every array 16-byte aligned: [goals][cost][terms][collisions][rows][costmaps][base rows]
   // (wlog: the wheel log beside `log`, the slope term in its wheel form; metrics: [E] host rows, the path
@@ -696,18 +702,19 @@ int score_logs(mppi_batch* b, const std::vector<ScoreGoal>& goals, const std::ve
   a.rows_out = d_rows;
   a.n = (int64_t)E;
   a.stride = stride;
-  a.cm = c->cmap.cm;
+  const BatchYardstick y = resolve_yardstick(c, yardstick);  // (w_orient: the context's set; a log is a body
+  a.cm = c->cmap.cm;                                         // path in either slope mode)
   a.cm_size = c->cmap.size;
-  a.hw = c->cmap.hw;
-  a.res_c = c->cmap.res;
-  a.vmax = p.v_max_linear;
-  a.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
-  a.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
-  a.w_path = yardstick ? yardstick->w_path : p.w_path;
-  a.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
-  a.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
-  a.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
-  a.w_orient = c->crit.w_orientation;  // the context's set; a log is a body path in either slope mode
+  a.hw = y.hw;
+  a.res_c = y.res_c;
+  a.vmax = y.vmax;
+  a.thr = y.thr;
+  a.pen = y.pen;
+  a.w_path = y.w_path;
+  a.w_slope = y.w_slope;
+  a.w_speed = y.w_speed;
+  a.w_obs = y.w_obs;
+  a.w_orient = y.w_orient;
   a.cost = d_cost;
   a.terms = d_terms;
   a.collisions = d_col;
@@ -958,20 +965,12 @@ int mppi_batch_set_tracking(mppi_batch* b, const mppi_batch_variant* yardstick, 
     for (BatchEpisode& r : b->host) r.steps_run = 0;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));  // recs is pageable and dies here
-  const mppi_params& p = c->p;
   BatchTrack& t = b->trk;
   t = BatchTrack{};
   t.max_steps = max_steps;
   t.runs_per_episode = runs_per_episode;
   t.keep_log = keep_log ? 1 : 0;
-  t.vmax = p.v_max_linear;  // the yardstick is taken here, as a scored list takes it
-  t.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
-  t.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
-  t.w_path = yardstick ? yardstick->w_path : p.w_path;
-  t.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
-  t.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
-  t.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
-  t.w_orient = c->crit.w_orientation;
+  t.y = resolve_yardstick(c, yardstick);  // the yardstick is taken here, as a scored list takes it
   b->trk_goal_tol = goal_tol;
   b->tracking = true;
   return MPPI_OK;
@@ -1597,19 +1596,8 @@ static int set_tasks(mppi_batch* b, int32_t n, const mppi_batch_task* tasks, boo
   b->res.assign(N, BatchTaskResult{});
   b->scored = scored;
   b->wbook = wb;
-  if (scored) {  // the yardstick is taken here (as score_logs takes it when it scores a log)
-    const mppi_params& p = c->p;
-    BatchScoredCampaign& y = b->yard;
-    y = BatchScoredCampaign{};
-    y.vmax = p.v_max_linear;
-    y.thr = yardstick ? yardstick->collision_threshold : p.collision_threshold;
-    y.pen = yardstick ? yardstick->collision_penalty : p.collision_penalty;
-    y.w_path = yardstick ? yardstick->w_path : p.w_path;
-    y.w_slope = yardstick ? yardstick->w_slope : p.w_slope;
-    y.w_speed = yardstick ? yardstick->w_speed : p.w_speed;
-    y.w_obs = yardstick ? yardstick->w_obstacle : p.w_obstacle;
-    y.w_orient = c->crit.w_orientation;
-  }
+  // the yardstick is taken here (as score_logs takes it when it scores a log)
+  if (scored) b->yard = resolve_yardstick(c, yardstick);
   return MPPI_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "mppi_cmd.h"
@@ -301,7 +302,14 @@ struct BatchNoisePlan {
 };
 hipError_t launch_batch_noise(const BatchArgs& b, int64_t k_offset, hipStream_t st, const BatchNoisePlan& np);
 hipError_t launch_batch_rollout(const RolloutArgs& a, const BatchArgs& b, size_t lds, hipStream_t st, int proj);
-hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, size_t lds, hipStream_t st);
+// The finish, ingest and claim kernels are templates on a form: a struct that is the kernel's last
+// argument, says what it is (kCampaign, kScored, kStep, kTracked, kWheels) and hands out its parts
+// (queue(), scored(), io(), track(), wheels(); each exists where its flag is set).  A new form is one
+// more struct and one more line of explicit instantiation in mppi_batch_kernels.h; DESIGN.md §3.7 has
+// the table.  The static_asserts beside the structs hold the kernel-argument layouts.
+struct BatchPlainRun {  // mppi_batch_run, and the ingest of mppi_batch_step_device: no part
+  static constexpr bool kCampaign = false, kScored = false, kStep = false, kTracked = false, kWheels = false;
+};
 // ---- the task queue of a batch (mppi_batch_set_tasks / _run_tasks) ----
 // The E episodes become lanes that work through N tasks: the lane whose task ends (goal reached, or
 // the task's step cap) writes the task's result and claims the next index of the list with one
@@ -342,11 +350,10 @@ struct BatchCampaign {
   int* ep_var;             // [E] BatchArgs::ep_var, writable
   BatchScene* rec;         // [E] BatchSceneTable::rec, writable
   int n;
+  static constexpr bool kCampaign = true, kScored = false, kStep = false, kTracked = false, kWheels = false;
+  __host__ __device__ const BatchCampaign& queue() const { return *this; }
 };
-// The first fill: E workgroups claim as a finishing lane does (one statement of the rule).
-hipError_t launch_batch_claim(const BatchArgs& b, const BatchCampaign& q, hipStream_t st);
-hipError_t launch_batch_finish_campaign(const FinishArgs& f, const BatchArgs& b, const BatchCampaign& q, size_t lds,
-                                        hipStream_t st);
+static_assert(sizeof(BatchCampaign) == 72, "BatchCampaign layout");
 // ---- a scored task list (mppi_batch_set_tasks_scored / _get_task_scores) ----
 // The advance lane of the finish kernel extends the four critic chains of the log scorer
 // (mppi_score_chain.h) by the row it logs, and writes the task's score row with its result: what
@@ -375,27 +382,36 @@ struct BatchTaskScore {  // one row per task, zero until the task ends (and for 
   double length;
 };
 static_assert(sizeof(BatchTaskScore) == 40, "BatchTaskScore layout");
-// The scored forms' own third kernel argument (BatchArgs does not grow): the queue, then the
-// yardstick as taken when the list was set, the costmap geometry of the run and the two tables.
+// What an executed path is scored against: the geometry of the context's costmap as it stands when the run
+// or the step is enqueued, and the limits and weights as taken when the list or tracking was set.  (The
+// costmap's pointer and size stay beside it in the two forms, where their kernels' arguments have them.)
+struct BatchYardstick {
+  float hw, res_c;
+  float vmax, thr, pen;
+  float w_path, w_slope, w_speed, w_obs, w_orient;
+};
+static_assert(sizeof(BatchYardstick) == 40, "BatchYardstick layout");
+// The scored form (BatchArgs does not grow): the queue, the two tables and the yardstick.
 struct BatchScoredCampaign {
   BatchCampaign q;          // q.log null: the list keeps no log and no row is written
   BatchScoreAcc* acc;       // [E]
   BatchTaskScore* score;    // [n]
   const float* cm;          // the context's costmap: a task without a costmap slot
   int cm_size;
-  float hw, res_c;
-  float vmax, thr, pen;
-  float w_path, w_slope, w_speed, w_obs, w_orient;
+  BatchYardstick y;
+  static constexpr bool kCampaign = true, kScored = true, kStep = false, kTracked = false, kWheels = false;
+  __host__ __device__ const BatchCampaign& queue() const { return q; }
+  __host__ __device__ const BatchScoredCampaign& scored() const { return *this; }
 };
-hipError_t launch_batch_claim_scored(const BatchArgs& b, const BatchScoredCampaign& s, hipStream_t st);
-hipError_t launch_batch_finish_scored(const FinishArgs& f, const BatchArgs& b, const BatchScoredCampaign& s,
-                                      size_t lds, hipStream_t st);
+static_assert(sizeof(BatchScoredCampaign) == 144 && offsetof(BatchScoredCampaign, acc) == 72 &&
+                  offsetof(BatchScoredCampaign, cm) == 88 && offsetof(BatchScoredCampaign, y.w_orient) == 136,
+              "BatchScoredCampaign layout");
 // ---- the device-resident step of a batch (mppi_batch_step_device) ----
 // One step of every set episode for a plant that is not the controller's own model: the ingest
 // kernel writes the caller's states into the episode records, the noise and rollout kernels run as
 // in any step, and the finish kernel's step form hands the command and the plan out instead of
-// advancing.  mppi_batch_io (include/mppi.h) field for field: device pointers, the finish form's
-// own third kernel argument (BatchArgs does not grow).
+// advancing.  mppi_batch_io (include/mppi.h) field for field: device pointers, the step form of the
+// finish and the second argument of every ingest (BatchArgs does not grow).
 struct BatchIo {
   const float* states;    // [E][11] mppi_state field order
   const int* mask;        // [E] or null
@@ -403,12 +419,10 @@ struct BatchIo {
   const uint64_t* seeds;  // [E] or null
   float* cmd;             // [E][2] or null
   float* plan;            // [E][4H + 12] or null
+  static constexpr bool kCampaign = false, kScored = false, kStep = true, kTracked = false, kWheels = false;
+  __host__ __device__ const BatchIo& io() const { return *this; }
 };
 static_assert(sizeof(BatchIo) == 48, "BatchIo layout");
-// is_set: [E] the host's "mppi_batch_set_episode was called" flags in device memory
-hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, hipStream_t st);
-hipError_t launch_batch_finish_step(const FinishArgs& f, const BatchArgs& b, const BatchIo& io, size_t lds,
-                                    hipStream_t st);
 // ---- tracked device steps (mppi_batch_set_tracking / _step_tracked) ----
 // The device step with the notion of a run: the ingest kernel's tracked form logs the row an ingested
 // state makes with the command the previous step wrote, extends the scorer's chains by it as the
@@ -433,9 +447,8 @@ struct BatchRunResult {  // one row per (episode, run ordinal), zero until the r
   BatchTaskScore s;      // zero for a run that took no step
 };
 static_assert(sizeof(BatchRunResult) == 96, "BatchRunResult layout");
-// The tracked ingest's own fourth kernel argument: the tables, the step's two optional arrays, the
-// yardstick as taken when tracking was set (the field names of BatchScoredCampaign: one scoring rule
-// serves both), and the context's costmap and DEM, which an episode's slots replace.
+// The tracked form of the ingest: the tables, the step's two optional arrays, the caps and the yardstick
+// as taken when tracking was set, and the context's costmap and DEM, which an episode's slots replace.
 struct BatchTrack {
   BatchTrackRec* rec;    // [E]
   int* runs;             // [E] runs ended per episode (may pass runs_per_episode: results were dropped)
@@ -445,27 +458,30 @@ struct BatchTrack {
   int max_steps, runs_per_episode, keep_log;
   int cm_size;
   const float* cm;       // the context's costmap: an episode without a costmap slot
-  float hw, res_c;
-  float vmax, thr, pen;
-  float w_path, w_slope, w_speed, w_obs, w_orient;
+  BatchYardstick y;
   const float* Z;        // the context's DEM: an episode without a DEM slot (z null only)
   int rows, grid;
   float x_min, y_min, res;
+  static constexpr bool kCampaign = false, kScored = false, kStep = false, kTracked = true, kWheels = false;
+  __host__ __device__ const BatchTrack& track() const { return *this; }
 };
-// The tracked step finish's third kernel argument: the io block and the records that take (v, w).
+static_assert(sizeof(BatchTrack) == 136 && offsetof(BatchTrack, cm) == 56 && offsetof(BatchTrack, y.w_orient) == 100 &&
+                  offsetof(BatchTrack, Z) == 104,
+              "BatchTrack layout");
+// The tracked step form of the finish: the io block and the records that take (v, w).
 struct BatchTrackedIo {
-  BatchIo io;
+  BatchIo base;
   BatchTrackRec* rec;  // [E]
+  static constexpr bool kCampaign = false, kScored = false, kStep = true, kTracked = true, kWheels = false;
+  __host__ __device__ const BatchIo& io() const { return base; }
+  __host__ __device__ BatchTrackRec* track() const { return rec; }
 };
-hipError_t launch_batch_ingest_tracked(const BatchArgs& b, const BatchIo& io, const int* is_set, const BatchTrack& t,
-                                       hipStream_t st);
-hipError_t launch_batch_finish_step_tracked(const FinishArgs& f, const BatchArgs& b, const BatchTrackedIo& io,
-                                            size_t lds, hipStream_t st);
+static_assert(sizeof(BatchTrackedIo) == 56 && offsetof(BatchTrackedIo, rec) == 48, "BatchTrackedIo layout");
 // ---- wheel contacts and path metrics of executed paths (mppi_batch_set_wheel_log /
 // _set_score_options) ----
 // Opt-in: a batch that turns none of them on launches the kernels above with the arguments above.  With
-// one on, the host picks the forms below, whose third (ingest: fourth) kernel argument is the form's own
-// block followed by BatchWheelOpts; every table is allocated only while its option is on.
+// one on, the host fills the forms below: the form they extend, followed by BatchWheelOpts; every table is
+// allocated only while its option is on.
 //   wlog     the wheel-contact log, parallel to the log: row n of a path's log has its contacts
 //            (lx, ly, lz, rx, ry, rz) in row n of the same index here.  Own model: floats 4H + 6 .. 4H + 11
 //            of the step's finish output (row 0 of left_wheel_sim / right_wheel_sim); tracked: formed by
@@ -488,29 +504,48 @@ struct BatchWheelOpts {
   float off;             // mppi_params wheel_offset (the tracked ingest forms the contacts)
   int pad;
 };
+static_assert(sizeof(BatchWheelOpts) == 40, "BatchWheelOpts layout");
 struct BatchWheelRun {  // the plain finish form's (mppi_batch_run with the wheel log on)
   BatchWheelOpts x;
+  static constexpr bool kCampaign = false, kScored = false, kStep = false, kTracked = false, kWheels = true;
+  __host__ __device__ const BatchWheelOpts& wheels() const { return x; }
 };
+static_assert(sizeof(BatchWheelRun) == 40, "BatchWheelRun layout");
 struct BatchWheelCampaign {
   BatchCampaign q;
   BatchWheelOpts x;
+  static constexpr bool kCampaign = true, kScored = false, kStep = false, kTracked = false, kWheels = true;
+  __host__ __device__ const BatchCampaign& queue() const { return q; }
+  __host__ __device__ const BatchWheelOpts& wheels() const { return x; }
 };
+static_assert(sizeof(BatchWheelCampaign) == 112 && offsetof(BatchWheelCampaign, x) == 72, "BatchWheelCampaign layout");
 struct BatchWheelScored {
   BatchScoredCampaign s;
   BatchWheelOpts x;
+  static constexpr bool kCampaign = true, kScored = true, kStep = false, kTracked = false, kWheels = true;
+  __host__ __device__ const BatchCampaign& queue() const { return s.q; }
+  __host__ __device__ const BatchScoredCampaign& scored() const { return s; }
+  __host__ __device__ const BatchWheelOpts& wheels() const { return x; }
 };
+static_assert(sizeof(BatchWheelScored) == 184 && offsetof(BatchWheelScored, x) == 144, "BatchWheelScored layout");
 struct BatchWheelTrack {
   BatchTrack t;
   BatchWheelOpts x;
+  static constexpr bool kCampaign = false, kScored = false, kStep = false, kTracked = true, kWheels = true;
+  __host__ __device__ const BatchTrack& track() const { return t; }
+  __host__ __device__ const BatchWheelOpts& wheels() const { return x; }
 };
-hipError_t launch_batch_finish_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelRun& w, size_t lds,
-                                      hipStream_t st);
-hipError_t launch_batch_finish_campaign_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelCampaign& w,
-                                               size_t lds, hipStream_t st);
-hipError_t launch_batch_finish_scored_wheels(const FinishArgs& f, const BatchArgs& b, const BatchWheelScored& w,
-                                             size_t lds, hipStream_t st);
-hipError_t launch_batch_ingest_tracked_wheels(const BatchArgs& b, const BatchIo& io, const int* is_set,
-                                              const BatchWheelTrack& t, hipStream_t st);
+static_assert(sizeof(BatchWheelTrack) == 176 && offsetof(BatchWheelTrack, x) == 136, "BatchWheelTrack layout");
+// One launcher per kernel, defined and explicitly instantiated for the forms above in mppi_batch_kernels.h.
+template <class Form>
+hipError_t launch_batch_finish(const FinishArgs& f, const BatchArgs& b, const Form& form, size_t lds, hipStream_t st);
+// is_set: [E] the host's "mppi_batch_set_episode was called" flags in device memory
+template <class Form>
+hipError_t launch_batch_ingest(const BatchArgs& b, const BatchIo& io, const int* is_set, const Form& form,
+                               hipStream_t st);
+// The first fill of a task list: E workgroups claim as a finishing lane does (one statement of the rule).
+template <class Form>
+hipError_t launch_batch_claim(const BatchArgs& b, const Form& form, hipStream_t st);
 
 hipError_t launch_bilinear(const float* Z, int rows, int grid, float x_min, float y_min, float res,
                            const float* xs, const float* ys, float* hs, int64_t n, hipStream_t st);

@@ -1308,8 +1308,29 @@ int mppi_batch_set_costmap(mppi_batch* b, int32_t slot, const float* cm_host) {
 
 int mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacles, int32_t n, double origin_x,
                              double origin_y, double r_robot, int32_t power, int32_t metric, float* out_host) {
+  return mppi_batch_build_costmap_hazard(b, slot, -1, obstacles, n, origin_x, origin_y, r_robot, power, metric, nullptr,
+                                         out_host, nullptr);
+}
+
+int mppi_batch_build_costmap_hazard(mppi_batch* b, int32_t slot, int32_t dem_slot, const double* obstacles, int32_t n,
+                                    double origin_x, double origin_y, double r_robot, int32_t power, int32_t metric,
+                                    const mppi_hazard* hz, float* out_host, uint8_t* mask_host) {
   if (int rc = slot_index(b, kSceneCostmap, slot)) return rc;
   mppi_ctx* c = b->c;
+  // the heights a hazard build reads: a DEM slot of the batch, or the context's DEM
+  DemView dem;
+  if (hz) {
+    if (dem_slot != -1) {
+      if (int rc = slot_index(b, kSceneDem, dem_slot)) return rc;
+      if (!b->dems[dem_slot].Z)
+        return fail(MPPI_ESTATE, "batch_build_costmap_hazard: dem_slot " + std::to_string(dem_slot) + " is empty");
+      dem = dem_view(b->dems[dem_slot]);
+    } else {
+      if (!c->dem.Z || c->dem.rows <= 0)
+        return fail(MPPI_ESTATE, "batch_build_costmap_hazard: no DEM bound: call mppi_set_dem first");
+      dem = dem_view(c->dem);
+    }
+  }
   if (int rc_q = quiesce(c)) return rc_q;
   HIP_TRY(hipSetDevice(c->device));
   // the builder's own resolution (mppi_build_costmap) must be the one the kernels index the slots with
@@ -1320,7 +1341,7 @@ int mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacle
   float* dst = nullptr;
   if (int rc = costmap_slot_buffer(b, slot, "batch_build_costmap", fresh, &dst)) return rc;
   if (int rc = build_costmap_into(c, obstacles, n, c->cmap.size, hw, origin_x, origin_y, r_robot, power, metric, dst,
-                                  out_host))
+                                  out_host, hz, &dem, mask_host))
     return rc;
   return costmap_slot_publish(b, slot, fresh);
 }

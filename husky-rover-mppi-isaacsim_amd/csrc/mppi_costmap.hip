@@ -18,11 +18,17 @@
 //     and a row pass (min over x' of (x - x')^2 + g(x')^2, searched outwards from x only while o^2
 //     can still improve the best), normalise and power in float64, one rounding to float32.
 // Both are integer-exact up to the normalisation; see DESIGN.md §3.6.
+//
+// Hazard (optional): between the raster and the distance, the steep cells of a
+// DEM on the device are counted per costmap cell, thresholded, grown by the exact integer distance
+// (the column and row passes of the exact metric) and ORed into the occupancy.
 #include <algorithm>
 #include <climits>
+#include <cstdint>
 #include <cstdlib>
 
 #include "mppi_costmap.h"
+#include "mppi_hazard.h"
 
 namespace mppi {
 
@@ -803,15 +809,245 @@ __global__ __launch_bounds__(CM_THREADS) void costmap_cv_scale_kernel(const floa
   }
 }
 
+// ------------------------------------------------------------- hazard: steep DEM cells (D15)
+// Count, per costmap cell, the DEM cells whose normal is steeper than the limit.  One streaming
+// pass over Z: a workgroup takes kHzCols columns (one float4 per thread and row; scalar loads when
+// the rows are not 16-byte aligned) and R rows, top to bottom; the row below is loaded once and kept
+// in registers as the next row's upper corners, kHzUnroll rows' loads are issued together, and the
+// one-column halo comes from the next lane (the wave's last lane and the row's last thread load or
+// clamp it).  nz is the normal table's (mppi_normal_table_kernel: corners clamped into the map, the
+// same float32 operations in the same order, no contraction), so the flag is the one a rollout
+// standing in the cell would derive.  The square root and the division are only run where they can
+// decide: nz = fl(res^2 / fl(sqrt(a))) is within 1.2e-7 relative of rho = res^2 / sqrt(a), and
+// comparing vz2 = fl(res^4) with fl(fl(c c) a) carries four roundings (under 3e-7 relative), so
+// vz2 > 1.0001 c^2 a means rho > c (1 + 4.9e-5) and nz > c, vz2 < 0.9999 c^2 a means nz < c; only a
+// cell inside that band, or one with a NaN or huge a, takes the IEEE sequence (valid while
+// res^4 is in [1e-15, 1e15] and a <= 1e15, so no product leaves the normal range; else every cell
+// takes it).
+// The flags are summed per thread over the rows of one costmap row and the neighbouring columns of
+// one costmap column (ci / rj are monotone), then in LDS counters over the workgroup's costmap
+// window, and reach the count plane as one integer atomicAdd per touched costmap cell and
+// workgroup.  Integer adds commute: the counts do not depend on the order.  A window that does not
+// fit the counters (a costmap much finer than the DEM) adds to the plane directly.
+template <bool VEC>
+__global__ __launch_bounds__(kHzThreads) void costmap_hazard_count_kernel(
+    const float* __restrict__ Z, int rows, int cols, float res, float cos_limit, const int32_t* __restrict__ ci,
+    const int32_t* __restrict__ rj, int R, int use_lds, int size, int32_t* __restrict__ cnt) {
+  __shared__ int32_t win[kHzLdsCounters];
+  __shared__ int red[4][kHzThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int i0 = blockIdx.x * kHzCols + 4 * tid;  // this thread's columns i0 .. i0 + 3
+  const int r0 = blockIdx.y * R, r1 = min(rows, r0 + R);
+  int I[4];
+  int ilo = INT_MAX, ihi = -1, jlo = INT_MAX, jhi = -1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    I[k] = i0 + k < cols ? ci[i0 + k] : -1;
+    if (I[k] >= 0) {
+      ilo = min(ilo, I[k]);
+      ihi = max(ihi, I[k]);
+    }
+  }
+  for (int r = r0 + tid; r < r1; r += kHzThreads) {
+    const int J = rj[r];
+    if (J >= 0) {
+      jlo = min(jlo, J);
+      jhi = max(jhi, J);
+    }
+  }
+  ilo = wave_min(ilo);
+  ihi = wave_max(ihi);
+  jlo = wave_min(jlo);
+  jhi = wave_max(jhi);
+  if (lane == 0) {
+    red[0][wv] = ilo;
+    red[1][wv] = ihi;
+    red[2][wv] = jlo;
+    red[3][wv] = jhi;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kHzThreads / 64; ++k) {
+    ilo = min(ilo, red[0][k]);
+    ihi = max(ihi, red[1][k]);
+    jlo = min(jlo, red[2][k]);
+    jhi = max(jhi, red[3][k]);
+  }
+  if (ihi < 0 || jhi < 0) return;  // (uniform) none of these DEM cells lies in the costmap
+  const int wi = ihi - ilo + 1, wj = jhi - jlo + 1;
+  const bool lds = use_lds && (int64_t)wi * wj <= kHzLdsCounters;
+  // row r (clamped into the map) at this thread's columns and the column after them
+  auto load_row = [&](int r, float (&q)[5]) __attribute__((always_inline)) {
+    const float* row = Z + (size_t)min(r, rows - 1) * cols;
+    if constexpr (VEC) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (i0 < cols) v = *reinterpret_cast<const float4*>(row + i0);  // cols % 4 == 0: all four inside
+      q[0] = v.x;
+      q[1] = v.y;
+      q[2] = v.z;
+      q[3] = v.w;
+      float h = __shfl_down(v.x, 1, 64);
+      if (lane == 63 || i0 + 4 >= cols) h = i0 + 4 < cols ? row[i0 + 4] : v.w;
+      q[4] = h;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) q[k] = row[min(i0 + k, cols - 1)];
+    }
+  };
+  // the first rows are on their way while the counters are cleared
+  float cur[5];
+  float nx[kHzUnroll][5];
+  load_row(r0, cur);
+#pragma unroll
+  for (int q = 0; q < kHzUnroll; ++q) load_row(r0 + q + 1, nx[q]);
+  if (lds) {
+    for (int k = tid; k < wi * wj; k += kHzThreads) win[k] = 0;
+    __syncthreads();
+  }
+  const float res_half_neg = (-res) / 2.0f;
+  const float res_sq = res * res;
+  const float vz2 = res_sq * res_sq;
+  const float c2 = cos_limit * cos_limit;
+  const bool band_ok = vz2 >= 1e-15f && vz2 <= 1e15f;
+  int acc[4] = {0, 0, 0, 0};
+  auto row_flags = [&](const float (&a)[5], const float (&b)[5]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float q0 = a[k], q1 = a[k + 1], q2 = b[k], q3 = b[k + 1];
+      const float vx = res_half_neg * (((q1 - q0) - q2) + q3);
+      const float vy = res_half_neg * (((q2 - q0) - q1) + q3);
+      const float a = (vx * vx + vy * vy) + vz2;
+      const float u = c2 * a;
+      const bool flat = vz2 > u * 1.0001f;
+      bool steep = vz2 < u * 0.9999f;
+      if (!(band_ok && a <= 1e15f && (flat || steep))) steep = !(res_sq / sqrtf(a) >= cos_limit);
+      acc[k] += (I[k] >= 0 && steep) ? 1 : 0;
+    }
+  };
+  // the sums of costmap row J: neighbouring columns of one costmap column together
+  auto flush = [&](int J) __attribute__((always_inline)) {
+    if (J < 0) return;
+    int run = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      run += acc[k];
+      acc[k] = 0;
+      if (k == 3 || I[k + 1] != I[k]) {
+        if (run > 0) {
+          if (lds)
+            atomicAdd(&win[(J - jlo) * wi + (I[k] - ilo)], run);
+          else
+            atomicAdd(&cnt[(size_t)J * size + I[k]], run);
+        }
+        run = 0;
+      }
+    }
+  };
+  int Jcur = -1;
+  for (int r = r0; r < r1; r += kHzUnroll) {
+    if (r > r0) {
+#pragma unroll
+      for (int q = 0; q < kHzUnroll; ++q) load_row(r + q + 1, nx[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < kHzUnroll; ++q) {
+      if (r + q < r1) {
+        const int J = rj[r + q];
+        if (J != Jcur) {
+          flush(Jcur);
+          Jcur = J;
+        }
+        if (J >= 0) {
+          if (q == 0)
+            row_flags(cur, nx[0]);
+          else
+            row_flags(nx[q > 0 ? q - 1 : 0], nx[q]);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) cur[k] = nx[kHzUnroll - 1][k];
+  }
+  flush(Jcur);
+  if (lds) {
+    __syncthreads();
+    for (int k = tid; k < wi * wj; k += kHzThreads) {
+      const int v = win[k];
+      if (v) atomicAdd(&cnt[(size_t)(jlo + k / wi) * size + (ilo + k % wi)], v);
+    }
+  }
+}
+
+// stage 0: H0 = count >= thr into `hocc` (the plane the exact passes read); with t_zero (T == 0)
+//   H1 = H0 goes straight into the occupancy.  stage 1: H1 = d2 <= thr, for a real distance only
+//   (d2 = inf2 marks a map without any H0 cell), ORed into the occupancy.
+// mask (optional): bit 0 H0, bit 1 H1, bit 2 the rock discs, which the raster left in `occ`.
+__global__ __launch_bounds__(CM_THREADS) void costmap_hazard_merge_kernel(const int32_t* __restrict__ src, int64_t n,
+                                                                         int stage, int32_t thr, int32_t inf2,
+                                                                         int t_zero, uint8_t* __restrict__ hocc,
+                                                                         uint8_t* __restrict__ occ,
+                                                                         uint8_t* __restrict__ mask) {
+  for (int64_t i = (int64_t)blockIdx.x * CM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * CM_THREADS) {
+    if (stage == 0) {
+      const int h = src[i] >= thr ? 1 : 0;
+      hocc[i] = (uint8_t)h;
+      if (mask) mask[i] = (uint8_t)(h | (t_zero ? h << 1 : 0) | (occ[i] ? 4 : 0));
+      if (t_zero && h) occ[i] = 1;
+    } else {
+      const int32_t d = src[i];
+      if (d <= thr && d < inf2) {
+        occ[i] = 1;
+        if (mask) mask[i] |= 2;
+      }
+    }
+  }
+}
+
+// The hazard passes, after the raster: sc.occ holds the rock discs and gains H1.
+hipError_t launch_costmap_hazard(const CostmapScratch& sc, int size, const CostmapHazard& hz, hipStream_t st) {
+  const size_t cells = (size_t)size * size;
+  int32_t* cnt = sc.d2;
+  uint8_t* hocc = reinterpret_cast<uint8_t*>(sc.lines);
+  hipError_t e = hipMemsetAsync(cnt, 0, cells * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  const int R = std::max(kHzUnroll, std::min(kHzMaxRows, hz.rows_per_group / kHzUnroll * kHzUnroll));
+  const dim3 grid((hz.cols + kHzCols - 1) / kHzCols, (hz.rows + R - 1) / R);
+  const bool vec = hz.cols % 4 == 0 && (reinterpret_cast<uintptr_t>(hz.Z) & 15) == 0;
+  if (hz.ev_count[0] && (e = hipEventRecord(hz.ev_count[0], st)) != hipSuccess) return e;
+  if (vec)
+    hipLaunchKernelGGL(costmap_hazard_count_kernel<true>, grid, dim3(kHzThreads), 0, st, hz.Z, hz.rows, hz.cols, hz.res,
+                       hz.cos_limit, hz.ci, hz.rj, R, hz.lds ? 1 : 0, size, cnt);
+  else
+    hipLaunchKernelGGL(costmap_hazard_count_kernel<false>, grid, dim3(kHzThreads), 0, st, hz.Z, hz.rows, hz.cols, hz.res,
+                       hz.cos_limit, hz.ci, hz.rj, R, hz.lds ? 1 : 0, size, cnt);
+  if (hz.ev_count[1] && (e = hipEventRecord(hz.ev_count[1], st)) != hipSuccess) return e;
+  const unsigned blocks = (unsigned)std::min<size_t>((cells + CM_THREADS - 1) / CM_THREADS, 256 * 8);
+  const int32_t inf2 = (2 * size + 1) * (2 * size + 1);
+  hipLaunchKernelGGL(costmap_hazard_merge_kernel, dim3(blocks), dim3(CM_THREADS), 0, st, cnt, (int64_t)cells, 0,
+                     hz.min_cells, inf2, hz.T == 0 ? 1 : 0, hocc, sc.occ, hz.mask);
+  if (hz.T > 0) {
+    const int nseg = (size + COSTMAP_SEG - 1) / COSTMAP_SEG;
+    const dim3 cgrid((size + CM_THREADS - 1) / CM_THREADS, nseg);
+    hipLaunchKernelGGL(costmap_colseg_kernel, cgrid, dim3(CM_THREADS), 0, st, hocc, size, sc.first, sc.last);
+    hipLaunchKernelGGL(costmap_colg_kernel, cgrid, dim3(CM_THREADS), 0, st, hocc, size, nseg, sc.first, sc.last, sc.g2);
+    hipLaunchKernelGGL(costmap_row_kernel, dim3(size), dim3(CM_THREADS), (size_t)size * sizeof(int32_t), st, sc.g2, size,
+                       sc.d2, sc.range);
+    hipLaunchKernelGGL(costmap_hazard_merge_kernel, dim3(blocks), dim3(CM_THREADS), 0, st, sc.d2, (int64_t)cells, 1, hz.T,
+                       inf2, 0, hocc, sc.occ, hz.mask);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_costmap_build(const CostmapScratch& sc, int n_obs, int size, int power, float* out,
-                                hipStream_t st, int metric) {
+                                hipStream_t st, int metric, const CostmapHazard* hz) {
   const size_t cells = (size_t)size * size;
   hipError_t e = hipMemsetAsync(sc.occ, 0, cells, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(costmap_raster_kernel, dim3(n_obs > 0 ? n_obs : 1), dim3(CM_THREADS), 0, st, sc.obs, n_obs,
                      sc.xs, size, sc.occ);
+  if (hz && (e = launch_costmap_hazard(sc, size, *hz, st)) != hipSuccess) return e;
   if (metric == COSTMAP_CHAMFER5 || metric == COSTMAP_CHAMFER5_RASTER) {
     float* dist = reinterpret_cast<float*>(sc.d2);
     const int lines = metric == COSTMAP_CHAMFER5;

@@ -64,6 +64,8 @@ struct CostmapBuffers {
   DeviceBuf<int32_t> first, last, g2, d2, range;
   DeviceBuf<uint32_t> lines;
   DeviceBuf<double> obs, xs;
+  DeviceBuf<int32_t> hz_tab;  // hazard build: ci[cols] then rj[rows] (mppi_hazard.h)
+  DeviceBuf<uint8_t> mask;    // hazard build: [size*size] H0 / H1 / disc bits, when the caller asks for them
   size_t cells_cap = 0;
   // Let go of the per-cell planes before larger ones are allocated (`lines` alone is 64 bytes per cell).
   void drop_planes() {
@@ -331,9 +333,18 @@ int batch_fill_dem(mppi_batch* b, int32_t slot, const char* who, const std::func
 int build_dem_into(hipStream_t st, const double* craters, int32_t n, int32_t grid, double half_width,
                    const float* base_host, float* dst, float* out_host, int32_t variant);
 // mppi_capi_costmap.cpp
+// heights on the device with their geometry, as a hazard build reads them (a context's DEM or a batch's slot)
+struct DemView {
+  const float* Z = nullptr;
+  int32_t rows = 0, cols = 0;
+  float x_min = 0, y_min = 0, res = 0;
+};
+inline DemView dem_view(const Dem& d) { return DemView{d.Z.get(), d.rows, d.cols, d.x_min, d.y_min, d.res}; }
+// hz == nullptr: the rock-only build (dem and mask_host are not looked at)
 int build_costmap_into(mppi_ctx* c, const double* obstacles, int32_t n, int32_t size, double half_width,
                        double origin_x, double origin_y, double r_robot, int32_t power, int32_t metric, float* dst,
-                       float* out_host);
+                       float* out_host, const mppi_hazard* hz = nullptr, const DemView* dem = nullptr,
+                       uint8_t* mask_host = nullptr);
 // mppi_capi_score.cpp
 int run_score(mppi_ctx* c, const ScoreArgs& a);
 

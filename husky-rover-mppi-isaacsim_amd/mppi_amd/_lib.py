@@ -98,6 +98,12 @@ class MppiCritics(C.Structure):
     _fields_ = [("slope_mode", C.c_int32), ("w_orientation", C.c_float)]
 
 
+class MppiHazard(C.Structure):
+    """mppi_hazard (include/mppi.h): the steep-terrain part of a hazard costmap."""
+    _fields_ = [("max_slope_deg", C.c_float), ("inflate", C.c_float), ("min_cells", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class MppiSampling(C.Structure):
     """mppi_sampling: the sampling plan of a context or of a variant row (12 bytes)."""
     _fields_ = [("antithetic", C.c_int32), ("nominal", C.c_int32), ("beta", C.c_float)]
@@ -167,6 +173,15 @@ _PROTOS = {
     "mppi_costmap_builder_build": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_double, C.c_double, C.c_int32, _FP, C.c_void_p, C.c_int32]),
     "mppi_costmap_builder_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mppi_build_costmap_hazard": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_int32, C.POINTER(MppiHazard), _FP,
+                                            C.POINTER(C.c_uint8), C.c_int32]),
+    "mppi_costmap_builder_build_hazard": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                    C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32,
+                                                    C.c_int32, C.c_float, C.c_float, C.c_float,
+                                                    C.POINTER(MppiHazard), _FP, C.c_void_p, C.POINTER(C.c_uint8),
+                                                    C.c_int32]),
+    "mppi_costmap_builder_hazard_count_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mppi_dem_builder_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
     "mppi_dem_builder_destroy": (None, [C.c_void_p]),
     "mppi_dem_builder_build": (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32, C.c_double, _FP, _FP, C.c_void_p,
@@ -209,6 +224,9 @@ _PROTOS = {
     "mppi_batch_set_costmap": (C.c_int, [C.c_void_p, C.c_int32, _FP]),
     "mppi_batch_build_costmap": (C.c_int, [C.c_void_p, C.c_int32, _DP, C.c_int32, C.c_double, C.c_double,
                                            C.c_double, C.c_int32, C.c_int32, _FP]),
+    "mppi_batch_build_costmap_hazard": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_double,
+                                                  C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                  C.POINTER(MppiHazard), _FP, C.POINTER(C.c_uint8)]),
     "mppi_batch_set_episode_scene": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "mppi_batch_set_episode_trajectories": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "mppi_batch_score": (C.c_int, [C.c_void_p, C.POINTER(MppiBatchVariant), C.POINTER(MppiState),
@@ -336,11 +354,38 @@ def _metric(m):
     return COSTMAP_METRICS[m]
 
 
+def make_hazard(hazard, r_robot):
+    """A hazard given as a dict or a scene.Hazard (max_slope_deg, inflate=None, min_cells=1) -> MppiHazard,
+    or None for None.  inflate None: r_robot + 0.1, the margin the reference gives its rocks."""
+    if hazard is None:
+        return None
+    if isinstance(hazard, MppiHazard):
+        return hazard
+    if isinstance(hazard, dict):
+        unknown = set(hazard) - {"max_slope_deg", "inflate", "min_cells"}
+        if unknown or "max_slope_deg" not in hazard:
+            raise ValueError(f"hazard: expected max_slope_deg and optionally inflate, min_cells; got {sorted(hazard)}")
+        get = hazard.get
+    else:
+        get = lambda k, d=None: getattr(hazard, k, d)   # noqa: E731
+    inflate = get("inflate", None)
+    return MppiHazard(float(get("max_slope_deg")), float(r_robot) + 0.1 if inflate is None else float(inflate),
+                      int(get("min_cells", 1)), 0)
+
+
+def _mask(size, want):
+    m = np.empty((int(size), int(size)), np.uint8) if want else None
+    return m, (None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+
 class CostmapBuilder:
     """Surface.create_obstacles_costmap (MPPI_isaac.py:361-378) on the GPU, no controller context needed.
 
     build(...) returns the size x size float32 costmap as an ndarray (the reference returns one);
     with out_device=<pointer> the map is written to caller-owned device memory instead.
+    With hazard= and dem=(z_device, rows, cols, x_min, y_min, resolution) the steep cells of those
+    device-resident heights join the rocks; return_mask adds the uint8 mask
+    (bit 0 H0, bit 1 H1, bit 2 rock disc) as a second result.
     """
 
     def __init__(self, device: int = 0):
@@ -351,16 +396,39 @@ class CostmapBuilder:
                "mppi_costmap_builder_create")
         self.h = h
 
-    def build(self, obstacles, origin, size, half_width, r_robot, power=20, out_device=None, metric="chamfer"):
+    def build(self, obstacles, origin, size, half_width, r_robot, power=20, out_device=None, metric="chamfer",
+              dem=None, hazard=None, return_mask=False):
         """metric "chamfer": the reference's cv2.distanceTransform(DIST_L2, 5); "exact": exact EDT."""
         obs, optr = _obstacles(obstacles)
         out = None if out_device is not None else np.empty((size, size), np.float32)
-        _check(self.lib, self.lib.mppi_costmap_builder_build(
+        hz = make_hazard(hazard, r_robot)
+        if hz is None:
+            if return_mask:
+                raise ValueError("return_mask needs a hazard")
+            _check(self.lib, self.lib.mppi_costmap_builder_build(
+                self.h, optr, obs.shape[0], int(size), float(half_width), float(origin[0]), float(origin[1]),
+                float(r_robot), int(power), None if out is None else _fp(out),
+                None if out_device is None else C.c_void_p(int(out_device)), _metric(metric)),
+                "mppi_costmap_builder_build")
+            return out
+        if dem is None:
+            raise ValueError("hazard: dem=(z_device, rows, cols, x_min, y_min, resolution) is needed")
+        z, rows, cols, x_min, y_min, res = dem
+        mask, mptr = _mask(size, return_mask)
+        _check(self.lib, self.lib.mppi_costmap_builder_build_hazard(
             self.h, optr, obs.shape[0], int(size), float(half_width), float(origin[0]), float(origin[1]),
-            float(r_robot), int(power), None if out is None else _fp(out),
-            None if out_device is None else C.c_void_p(int(out_device)), _metric(metric)),
-            "mppi_costmap_builder_build")
-        return out
+            float(r_robot), int(power), C.c_void_p(int(z) or None), int(rows), int(cols), float(x_min), float(y_min),
+            float(res), C.byref(hz), None if out is None else _fp(out),
+            None if out_device is None else C.c_void_p(int(out_device)), mptr, _metric(metric)),
+            "mppi_costmap_builder_build_hazard")
+        return (out, mask) if return_mask else out
+
+    def hazard_count_ms(self):
+        """Device time of the steep-cell count kernel alone in the last hazard build."""
+        ms = C.c_double()
+        _check(self.lib, self.lib.mppi_costmap_builder_hazard_count_ms(self.h, C.byref(ms)),
+               "mppi_costmap_builder_hazard_count_ms")
+        return ms.value
 
     def last_ms(self):
         ms = C.c_double()
@@ -636,17 +704,30 @@ class Engine:
         self.costmap_shape = (size, size)
 
     def build_costmap(self, obstacles, origin, size, half_width, r_robot, power=20, copy_out=True,
-                      metric="chamfer"):
+                      metric="chamfer", hazard=None, return_mask=False):
         """Surface.create_obstacles_costmap + costmap_wp.assign in one device pass
-        (visual_terrain_stack_full_terrain.py:561-563); returns the map if copy_out."""
+        (visual_terrain_stack_full_terrain.py:561-563); returns the map if copy_out.
+        hazard (a dict or scene.Hazard): the steep cells of the bound DEM, read in place, join the
+        rocks; return_mask: (map, uint8 mask with bit 0 H0, bit 1 H1, bit 2 rock disc)."""
         obs, optr = _obstacles(obstacles)
         out = np.empty((size, size), np.float32) if copy_out else None
-        self._c(self.lib.mppi_build_costmap(self.ctx, optr, obs.shape[0], int(size), float(half_width),
-                                            float(origin[0]), float(origin[1]), float(r_robot), int(power),
-                                            None if out is None else _fp(out), _metric(metric)),
-                "mppi_build_costmap")
+        hz = make_hazard(hazard, r_robot)
+        if hz is None:
+            if return_mask:
+                raise ValueError("return_mask needs a hazard")
+            self._c(self.lib.mppi_build_costmap(self.ctx, optr, obs.shape[0], int(size), float(half_width),
+                                                float(origin[0]), float(origin[1]), float(r_robot), int(power),
+                                                None if out is None else _fp(out), _metric(metric)),
+                    "mppi_build_costmap")
+            self.costmap_shape = (int(size), int(size))
+            return out
+        mask, mptr = _mask(size, return_mask)
+        self._c(self.lib.mppi_build_costmap_hazard(self.ctx, optr, obs.shape[0], int(size), float(half_width),
+                                                   float(origin[0]), float(origin[1]), float(r_robot), int(power),
+                                                   C.byref(hz), None if out is None else _fp(out), mptr,
+                                                   _metric(metric)), "mppi_build_costmap_hazard")
         self.costmap_shape = (int(size), int(size))
-        return out
+        return (out, mask) if return_mask else out
 
     def build_dem(self, bumps, grid_size, half_width, base=None, copy_out=True, variant="mfma"):
         """Surface.create_surface + set_dem in one device pass (mppi_build_dem): the crater field is
@@ -1099,6 +1180,28 @@ class Batch:
             self.h, int(slot), optr, obs.shape[0], float(origin[0]), float(origin[1]), float(r_robot), int(power),
             _metric(metric), None if out is None else _fp(out)), "mppi_batch_build_costmap")
         return out
+
+    def build_costmap_hazard(self, slot, obstacles, origin, r_robot, hazard, dem=-1, power=20, metric="chamfer",
+                             copy_out=False, return_mask=False):
+        """build_costmap with the steep cells of DEM slot `dem` (-1: the engine's DEM), read on the device,
+        joining the rocks (hazard: a dict or scene.Hazard, None: build_costmap).  Returns
+        the map if copy_out (else None); with return_mask (map or None, uint8 mask: bit 0 H0, bit 1 H1,
+        bit 2 rock disc).  (build_costmap keeps its parameter list; this is its hazard form.)"""
+        hz = make_hazard(hazard, r_robot)
+        if hz is None:
+            if return_mask:
+                raise ValueError("return_mask needs a hazard")
+            return self.build_costmap(slot, obstacles, origin, r_robot, power, metric, copy_out)
+        obs, optr = _obstacles(obstacles)
+        if self.engine.costmap_shape is None:
+            raise RuntimeError("costmap slot: the engine has no costmap yet (a slot takes its geometry)")
+        out = np.empty(self.engine.costmap_shape, np.float32) if copy_out else None
+        mask, mptr = _mask(self.engine.costmap_shape[0], return_mask)
+        _check(self.lib, self.lib.mppi_batch_build_costmap_hazard(
+            self.h, int(slot), int(dem), optr, obs.shape[0], float(origin[0]), float(origin[1]), float(r_robot),
+            int(power), _metric(metric), C.byref(hz), None if out is None else _fp(out), mptr),
+            "mppi_batch_build_costmap_hazard")
+        return (out, mask) if return_mask else out
 
     def set_variants(self, variants):
         """The batch's variant table: a list of MppiBatchVariant or dicts (make_variant's arguments);

@@ -154,6 +154,9 @@ class Surface:
     device = 0
     # distance metric of the costmap builder: "chamfer" = cv2.distanceTransform(DIST_L2, 5) (reference)
     costmap_metric = "chamfer"
+    # steep terrain as no-go cells of the costmap: None (the reference: rocks only),
+    # or a scene.Hazard / dict that MPPI_Controller.rebuild_costmap and rock-list costmap slots apply
+    hazard = None
 
     def create_obstacles_costmap(self, obstacles, origin):
         """MPPI_isaac.py:361-378 on the GPU (csrc/mppi_costmap.hip): disc raster, cv2.distanceTransform
@@ -166,6 +169,9 @@ class Surface:
         self.obstacles = obstacles
         return b.build(obstacles, origin, self.costmap_size, self.half_width, self.r_robot, power=20,
                        metric=self.costmap_metric)
+
+
+_SURFACE = object()   # rebuild_costmap(hazard=): "whatever the surface says"
 
 
 # =====================================================================  Robot
@@ -368,30 +374,43 @@ class MPPI_Controller:
 
     def _fill_costmap_slot(self, batch, slot, cm):
         """One entry of run_batch's `costmaps` into the batch's costmap slot: an array, or a rock list
-        built on the device with the surface's robot radius and costmap metric."""
+        built on the device with the surface's robot radius and costmap metric.  A dict entry
+        {"obstacles": ..., "origin": ..., "hazard": ..., "dem": k} adds the steep cells of DEM slot k
+        (-1 or absent: the engine's DEM) by the hazard rule (absent: the surface's `hazard`); the DEM
+        slots are filled first, so a crater field and its matching map never leave the device."""
         shape = self.engine.costmap_shape
         if _is_costmap_array(cm, shape):
             batch.set_costmap(slot, np.asarray(cm, np.float32).reshape(shape))
             return
-        rocks, origin = (cm["obstacles"], cm.get("origin", (0.0, 0.0))) if isinstance(cm, dict) else (cm, (0.0, 0.0))
-        batch.build_costmap(slot, rocks, origin, self.surface.r_robot, 20,
-                            metric=getattr(self.surface, "costmap_metric", "chamfer"))
+        hazard, dem = getattr(self.surface, "hazard", None), -1
+        if isinstance(cm, dict):
+            rocks, origin = cm["obstacles"], cm.get("origin", (0.0, 0.0))
+            hazard, dem = cm.get("hazard", hazard), int(cm.get("dem", -1))
+        else:
+            rocks, origin = cm, (0.0, 0.0)
+        batch.build_costmap_hazard(slot, rocks, origin, self.surface.r_robot, hazard, dem, 20,
+                                   metric=getattr(self.surface, "costmap_metric", "chamfer"))
 
     def _assign_costmap(self, flat):
         self.surface.costmap = np.asarray(flat, np.float32).reshape(
             self.surface.costmap_size, self.surface.costmap_size)
         self._upload_costmap(self.surface.costmap)
 
-    def rebuild_costmap(self, obstacles, origin):
+    def rebuild_costmap(self, obstacles, origin, hazard=_SURFACE):
         """surface.costmap = surface.create_obstacles_costmap(rocks, origin) + costmap_wp.assign(...)
         (visual_terrain_stack_full_terrain.py:561-563) in one device pass: the map is built in the
-        engine's own costmap buffer (no upload) and copied back once for surface.costmap."""
+        engine's own costmap buffer (no upload) and copied back once for surface.costmap.
+        hazard (default: surface.hazard; None: rocks only): the steep cells of the bound DEM, as it
+        is on the device now, join the rocks.  A DEM written later (dem_updated,
+        a new terrain block) does not change the map: call this again."""
         if self.engine is None:
             raise RuntimeError("call warp_setup() first")
         s = self.surface
         s.obstacles = obstacles
+        if hazard is _SURFACE:
+            hazard = getattr(s, "hazard", None)
         s.costmap = self.engine.build_costmap(obstacles, origin, s.costmap_size, s.half_width, s.r_robot, 20,
-                                              metric=getattr(s, "costmap_metric", "chamfer"))
+                                              metric=getattr(s, "costmap_metric", "chamfer"), hazard=hazard)
         return s.costmap
 
     @property

@@ -117,6 +117,96 @@ def crater_dem_separable(grid_size, half_width, bumps, base=None):
     return Z.astype(np.float32)
 
 
+class Hazard:
+    """Steep terrain as no-go cells of the obstacle costmap: DEM cells whose
+    normal is steeper than max_slope_deg, counted into costmap cells (>= min_cells to qualify) and
+    grown by `inflate` metres (None: r_robot + 0.1, the margin the reference gives its rocks).
+    Wherever a costmap is built on the device (Engine / Batch / CostmapBuilder / rebuild_costmap,
+    costmaps= entries) `hazard=` takes one of these or the same fields as a dict."""
+
+    def __init__(self, max_slope_deg, inflate=None, min_cells=1):
+        self.max_slope_deg = float(max_slope_deg)
+        self.inflate = None if inflate is None else float(inflate)
+        self.min_cells = int(min_cells)
+
+    def __repr__(self):
+        return f"Hazard(max_slope_deg={self.max_slope_deg}, inflate={self.inflate}, min_cells={self.min_cells})"
+
+
+def hazard_steep(Z, resolution, max_slope_deg):
+    """Steep DEM cells: cell (j, i) is steep iff !(nz >= c), nz the z component of the rollout's
+    normal in that cell (projection_warp.py:129-151 on the corners (j, i), (j, i+1), (j+1, i),
+    (j+1, i+1) clamped into the map, float32 in the reference's order) and
+    c = float32(cos(max_slope_deg pi / 180)).  A NaN nz (non-finite heights) is steep."""
+    Z = np.asarray(Z, np.float32)
+    rows, cols = Z.shape
+    r1 = np.minimum(np.arange(rows) + 1, rows - 1)
+    c1 = np.minimum(np.arange(cols) + 1, cols - 1)
+    q0, q1, q2, q3 = Z, Z[:, c1], Z[r1, :], Z[r1][:, c1]
+    res = np.float32(resolution)
+    hr = (-res) / np.float32(2.0)
+    rs = res * res
+    with np.errstate(all="ignore"):
+        vx = hr * (((q1 - q0) - q2) + q3)
+        vy = hr * (((q2 - q0) - q1) + q3)
+        nz = rs / np.sqrt((vx * vx + vy * vy) + rs * rs)
+        c = np.float32(np.cos(np.float64(np.float32(max_slope_deg)) * np.pi / 180.0))
+        return ~(nz >= c)
+
+
+def hazard_tables(rows, cols, x_min, y_min, resolution, size, half_width):
+    """(ci[cols], rj[rows]): the costmap column / row the centre of a DEM column / row falls into,
+    in the frame of the rollout's costmap lookup (column from x + half_width, row from
+    -y + half_width), float64; -1 outside [0, size)."""
+    hw = float(half_width)
+    rc = 2 * hw / size
+    x_min, y_min, res = (float(np.float32(v)) for v in (x_min, y_min, resolution))
+    ci = np.floor((x_min + (np.arange(cols) + 0.5) * res + hw) / rc)
+    rj = np.floor((hw - (-y_min - (np.arange(rows) + 0.5) * res)) / rc)
+    ci = np.where((ci >= 0) & (ci < size), ci, -1).astype(np.int32)
+    rj = np.where((rj >= 0) & (rj < size), rj, -1).astype(np.int32)
+    return ci, rj
+
+
+def hazard_occupancy(Z, x_min, y_min, resolution, size, half_width, max_slope_deg, min_cells=1, inflate=0.0):
+    """The hazard rule on the CPU, the yardstick of mppi_build_costmap_hazard:
+    returns (H0, H1), size x size bool.  H0: costmap cells that collected >= min_cells steep DEM
+    cells (hazard_steep, hazard_tables).  H1: cells whose exact squared cell distance to the nearest
+    H0 cell is <= T = floor((inflate / rc)^2), rc = 2 half_width / size (a disc dilation; H0 empty:
+    H1 empty, inflate 0: H1 = H0)."""
+    Z = np.asarray(Z, np.float32)
+    size = int(size)
+    steep = hazard_steep(Z, resolution, max_slope_deg)
+    ci, rj = hazard_tables(Z.shape[0], Z.shape[1], x_min, y_min, resolution, size, half_width)
+    ok = steep & (rj >= 0)[:, None] & (ci >= 0)[None, :]
+    jj, ii = np.nonzero(ok)
+    cnt = np.zeros((size, size), np.int64)
+    np.add.at(cnt, (rj[jj], ci[ii]), 1)
+    H0 = cnt >= int(min_cells)
+    rc = 2 * float(half_width) / size
+    T = int(np.floor((float(np.float32(inflate)) / rc) ** 2))
+    if T == 0 or not H0.any():
+        return H0, H0.copy()
+    # vertical distance to the nearest H0 cell of the column, then the columns within sqrt(T)
+    idx = np.arange(size, dtype=np.int64)[:, None]
+    far = 4 * size
+    up = np.maximum.accumulate(np.where(H0, idx, -far), axis=0)
+    dn = np.minimum.accumulate(np.where(H0, idx, far)[::-1], axis=0)[::-1]
+    g = np.minimum(idx - up, dn - idx)
+    g2 = g * g
+    H1 = np.zeros_like(H0)
+    s = int(np.floor(np.sqrt(T)))
+    while (s + 1) * (s + 1) <= T:
+        s += 1
+    for o in range(-min(s, size - 1), min(s, size - 1) + 1):
+        lim = T - o * o
+        if lim < 0:
+            continue
+        src = g2[:, max(0, -o):size - max(0, o)] <= lim      # H0 column x' = x - o reaches column x
+        H1[:, max(0, o):size - max(0, -o)] |= src
+    return H0, H1
+
+
 def random_obstacles(n=750, seed=99, extent=50.0, r_max=0.4):
     """MPPI_OO_current.py:721-725: [x, y, r] with RandomState(seed)."""
     rng = np.random.RandomState(seed)

@@ -181,6 +181,54 @@ int mppi_costmap_builder_build(mppi_costmap_builder* b, const double* obstacles,
 /* Device time (HIP events) of the builder's last build, in milliseconds. */
 int mppi_costmap_builder_last_ms(mppi_costmap_builder* b, double* ms);
 
+/* ---- hazard costmap: steep terrain joins the rocks ----
+ * The thesis's terrain scenarios ("keep avoiding steep craters, but tolerate small ones and gentle
+ * inclines") as the controller's hard constraint: the steep cells of a DEM that is already on the
+ * device become occupied cells of the obstacle costmap, in the same pass that rasters the rocks.
+ *
+ * Steep: DEM cell (j, i) is steep iff !(nz >= c), nz the z component of the normal the rollout reads
+ * when it stands in that cell (entry (j + 1, i + 1) of the normal table, the same float32 operations)
+ * and c = (float)cos(max_slope_deg pi / 180); a NaN nz (non-finite heights) is steep.
+ * Which costmap cell: the frame of the rollout's own costmap lookup (column from x + half_width,
+ * row from -y + half_width; NOT the axis-swapped origin frame of the rock list), at the cell's
+ * centre: with rc = 2 half_width / size, in float64,
+ *   column floor((x_min + (i + 0.5) res + half_width) / rc),
+ *   row    floor((half_width - (-y_min - (j + 0.5) res)) / rc);
+ * a DEM cell whose index falls outside [0, size) is dropped.
+ * H0: costmap cells that collected >= min_cells steep cells.  H1: cells whose exact squared cell
+ * distance to the nearest H0 cell is <= T = floor((inflate / rc)^2) (H0 empty: H1 empty; inflate
+ * = 0: H1 = H0).  Occupancy = H1 | rock discs; distance, normalisation and power as before, for
+ * every metric.  No occupied cell at all gives what the rock-only build gives.
+ *
+ * hz == NULL makes each function exactly its counterpart above.  MPPI_EINVAL, naming the field:
+ * max_slope_deg not finite or outside (0, 90), inflate not finite or negative, T beyond int32,
+ * min_cells < 1, reserved != 0.  MPPI_ESTATE: no DEM bound / the named DEM slot is empty.
+ * mask_host [size*size] (may be NULL): bit 0 H0, bit 1 H1, bit 2 inside a rock disc.
+ * mppi_build_costmap_hazard reads the context's bound DEM in place, owned or borrowed
+ * (mppi_set_dem_device).  The builder object takes the heights as a device pointer with their
+ * geometry (rows x cols float32, row-major); mppi_costmap_builder_last_ms covers the hazard passes.
+ * A costmap is a snapshot: mppi_dem_updated and a DEM rebinding do not rebuild it.  The caller
+ * rebuilds after the terrain changed. */
+typedef struct mppi_hazard {
+  float   max_slope_deg; /* cells steeper than this are no-go; in (0, 90) */
+  float   inflate;       /* metres the steep region is grown by (the reference's rock margin: r_robot + 0.1) */
+  int32_t min_cells;     /* steep DEM cells a costmap cell must collect; >= 1 */
+  int32_t reserved;      /* 0 */
+} mppi_hazard;
+int mppi_build_costmap_hazard(mppi_ctx* ctx, const double* obstacles, int32_t n, int32_t size,
+                              double half_width, double origin_x, double origin_y, double r_robot,
+                              int32_t power, const mppi_hazard* hz, float* out_host, uint8_t* mask_host,
+                              int32_t metric);
+int mppi_costmap_builder_build_hazard(mppi_costmap_builder* b, const double* obstacles, int32_t n,
+                                      int32_t size, double half_width, double origin_x, double origin_y,
+                                      double r_robot, int32_t power, const float* z_device, int32_t rows,
+                                      int32_t cols, float x_min, float y_min, float resolution,
+                                      const mppi_hazard* hz, float* out_host, float* out_device,
+                                      uint8_t* mask_host, int32_t metric);
+/* Device time (HIP events) of the steep-cell count kernel alone in the builder's last build, in
+ * milliseconds: the one pass over the heights (0 after a build without hz). */
+int mppi_costmap_builder_hazard_count_ms(mppi_costmap_builder* b, double* ms);
+
 /* ---- on-device crater-field DEM ----
  * Surface.create_surface(bumps) (MPPI_isaac.py:307-356) on the GPU.  craters: n rows of
  * (cx, cy, height, width) float64, host memory: bump_center, bump_height, bump_width of the
@@ -534,6 +582,16 @@ int  mppi_batch_set_costmap(mppi_batch* b, int32_t slot, const float* cm_host);
 int  mppi_batch_build_costmap(mppi_batch* b, int32_t slot, const double* obstacles, int32_t n,
                               double origin_x, double origin_y, double r_robot, int32_t power,
                               int32_t metric, float* out_host);
+/* mppi_batch_build_costmap with the steep cells of a DEM (mppi_build_costmap_hazard): dem_slot names
+ * the batch's DEM slot whose heights are read in place (-1: the context's DEM), so a crater field
+ * built into a slot (mppi_batch_build_dem) and its matching costmap never leave the device.
+ * hz == NULL is exactly mppi_batch_build_costmap (dem_slot is then not looked at).  MPPI_ESTATE
+ * when the DEM slot is empty or no DEM is bound; MPPI_EINVAL for a dem_slot outside the table.
+ * out_host and mask_host may be NULL. */
+int  mppi_batch_build_costmap_hazard(mppi_batch* b, int32_t slot, int32_t dem_slot, const double* obstacles,
+                                     int32_t n, double origin_x, double origin_y, double r_robot,
+                                     int32_t power, int32_t metric, const mppi_hazard* hz, float* out_host,
+                                     uint8_t* mask_host);
 /* mppi_build_dem into DEM slot `slot`, with the context DEM's geometry: the context's DEM must be square
  * with x_min = y_min = -(float)half_width and resolution (float)(2*half_width/rows) (MPPI_EINVAL
  * otherwise); MPPI_ESTATE without a context DEM.  Everything else as mppi_batch_set_dem (replacing a

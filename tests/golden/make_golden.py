@@ -29,9 +29,13 @@ step_small.npz
     Regression vectors of the CPU restatement (oracle/mppi_ref.py) for whole
     MPPI steps on a small self-contained scene (200^2 DEM, 25^2 costmap stored
     in the file): 3D/2D, far/near goal, injected controls, ragged K and odd H.
-    These are NOT reference outputs (Warp cannot run offline); they freeze the
-    restatement that the primitives above pin, and the GPU tests compare the
-    HIP engine with them bit for bit.
+    These are NOT reference outputs; they freeze the restatement that the
+    primitives above pin, and the GPU tests compare the HIP engine with them
+    bit for bit.  Whole steps that ARE reference outputs are made by the
+    script beside this one, make_warp_golden.py -> ref_warp_steps.npz: the
+    reference's own Warp kernels and host class run under the project's Warp
+    stand-in (oracle/warp_standin.py), and the restatement
+    is held to them bit for bit (tests/test_reference_warp_oracle.py).
 """
 from __future__ import annotations
 
